@@ -3,17 +3,24 @@
 bench.py -- TOD samples/s through one P^T N^-1 P matvec (BASELINE.json metric) on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5]
-                    [--scaling weak|strong]
+                    [--scaling weak|strong] [--dump-outputs DIR] [--full]
 
 A "step" is one application of A = P^T N^-1 P to a map-domain vector with all inputs
-already resident in HBM.  N > 1: launched by torch.distributed.run, one rank per GPU; a step is
-the local matvec of the rank's block-aligned TOD shard followed by the RCCL all-reduce of the
-map.  --scaling weak (default): every rank owns a shard of the configuration's per-GPU size
-(C4: 1e8 samples per GPU); --scaling strong: the configuration's TOTAL is cut into N shards
-(C4: 1e8 samples over N ranks; C5: 1e9 over 8).  With N > 1 the JSON line carries the other
-mode's point too ("other_scaling_point"), the backend and world size torch.distributed
-reports, and the exposed all-reduce time (step minus the local matvec).  Rank 0 prints ONE
-JSON line.
+already resident in HBM.  A plain run sets up, runs W warm-up steps and K timed steps and prints
+the headline line (`value`, `ms_per_step`).  --full adds every other leg: per-kernel stage times and
+the roofline (with the rocprofv3 --pmc traffic children), PCG and two-level PCG, filters, the
+secondary hit maps, the CPU baselines, the full-size parity with the CPU oracle and, with N > 1,
+the exposed collective time and the other layout's and scaling mode's points.  --dump-outputs DIR
+writes what the last timed step returned, A x, as DIR/A_x.npy (float64; inputs are seeded, so two
+builds can be compared output for output).
+
+N > 1: launched by torch.distributed.run, one rank per GPU; a step is the local matvec of the
+rank's block-aligned TOD shard followed by the RCCL all-reduce of the map.  --scaling weak
+(default): every rank owns a shard of the configuration's per-GPU size (C4: 1e8 samples per GPU);
+--scaling strong: the configuration's TOTAL is cut into N shards (C4: 1e8 samples over N ranks;
+C5: 1e9 over 8).  With N > 1 the JSON line carries the backend and world size torch.distributed
+reports and, with --full, the other mode's point too ("other_scaling_point") and the exposed
+all-reduce time (step minus the local matvec).  Rank 0 prints ONE JSON line.
 
 Workloads (BASELINE.json configs; synthetic inputs after utilities_functions.py:99-212:
 uniform-random pixel per sample, HWP angle ramp, d ~ U[0,1)):
@@ -43,6 +50,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E, /opt/skills/guides/MI355X_MICROARCH.md
+MAX_DUMP_VALUES = 7_500_000    # --dump-outputs: at most 60 MB of float64 per run
 
 CONFIGS = {
     "c2": dict(nside=128, nt=10_000_000, nb=100, lam=0, total=10_000_000, total_nb=100,
@@ -95,6 +103,25 @@ def synth_inputs(torch, dev, npix, nt, nb, lam, rank=0):
     bands = [toeplitz_band(lam, rng) for _ in range(nb)] if lam else None
     diag = None if lam else rng.random(nb) + 0.5
     return dict(gen=gen, rng=rng, theta0=theta0, pix=pix, phi=phi, d=d, bands=bands, diag=diag)
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each host array as out_dir/<name>.npy in float64.  An array of more than
+    MAX_DUMP_VALUES values is cut to a fixed sample (seeded choice of indices, kept in index order),
+    the same for every run of the same arguments.  Returns {name: what was written}."""
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64).ravel()
+        rec = {"values": int(a.size), "of": int(a.size)}
+        if a.size > MAX_DUMP_VALUES:
+            idx = np.sort(np.random.default_rng(20161202).choice(a.size, MAX_DUMP_VALUES, replace=False))
+            a = a[idx]
+            rec.update(values=int(a.size), sample="np.sort(np.random.default_rng(20161202).choice(%d, %d, "
+                                                  "replace=False))" % (rec["of"], MAX_DUMP_VALUES))
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = rec
+    return written
 
 
 def hbm_budget_gb(nt_rank, n, r, arnoldi_steps, world, layout):
@@ -305,6 +332,13 @@ def main():
     ap.add_argument("--fft-len", type=int, default=0)
     ap.add_argument("--toeplitz", default="fused", choices=["fused", "rocfft"],
                     help="overlap-save implementation for the Toeplitz configs")
+    ap.add_argument("--full", action="store_true",
+                    help="run every leg beside the headline (stages, roofline and PMC traffic, PCG, filters, "
+                         "secondary hit maps, CPU baselines, full-size parity, N > 1 extra points); the --no-* "
+                         "options above switch legs of a --full run off")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the result of the last timed step, A x, to DIR/A_x.npy (float64; above %d "
+                         "values a fixed seeded sample of them, in index order)" % MAX_DUMP_VALUES)
     args = ap.parse_args()
     if args.fft_len:
         os.environ["CM2_FFT_LEN"] = str(args.fft_len)
@@ -319,7 +353,7 @@ def main():
     # of an exec chain on this pool: rocprofv3 is a launcher that re-execs its target).  The dominant kernel of a
     # configuration is known from its noise model; the result is matched against the measured one below.
     traffic_pre = None
-    if (args.gpus == 1 and "WORLD_SIZE" not in os.environ and not (args.no_traffic or args.no_cpu)
+    if (args.full and args.gpus == 1 and "WORLD_SIZE" not in os.environ and not (args.no_traffic or args.no_cpu)
             and not under_profiler()):
         pre_regex = "k_os_real" if (CONFIGS[args.config]["lam"] and args.toeplitz == "fused") else (
             "k_PtNP_sell" if not CONFIGS[args.config]["lam"] else None)
@@ -486,7 +520,7 @@ def main():
                     npix_c=npix_c, P=P, Mbd=Mbd, A_local=A_local, A=A, n=n, x=x, rng=rng,
                     gen=gen, theta0=theta0, setup=tm, sh=sh, A_repl=A_repl, A_rows=A_rows, x_rows=x_rows)
 
-    def timed(A, x, steps, warmup):
+    def timed(A, x, steps, warmup, keep_output=False):
         for _ in range(warmup):
             y = A * x
         barrier()
@@ -508,6 +542,9 @@ def main():
             tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
             elapsed = float(tmax.item())
+        # (the last step's result, kept for --dump-outputs: a persistent-output operator overwrites it at
+        #  its next application, so it is copied now, after the clock has stopped)
+        timed.last_output = y.clone() if keep_output else None
         del y
         return elapsed
 
@@ -527,7 +564,7 @@ def main():
     sh, rows = S["sh"], (args.layout == "rows" and world > 1)
     x_in = S["x_rows"] if rows else x                # the vector the distributed operator acts on
     # ---- timed region: W warmup + exactly K steps ------------------------------------
-    elapsed = timed(A, x_in, args.steps, args.warmup)
+    elapsed = timed(A, x_in, args.steps, args.warmup, keep_output=bool(args.dump_outputs))
     ms_per_step = 1e3 * elapsed / args.steps
     nt_all = nt
     if world > 1:
@@ -536,14 +573,26 @@ def main():
         nt_all = int(tot.item())
     value = nt_all / (elapsed / args.steps)
 
-    # exposed all-reduce: the same K steps of the local matvec alone
+    # ---- --dump-outputs: the map A x of the last timed step (rank 0; row-sharded: gathered first) ----
+    dumped = None
+    if args.dump_outputs:
+        y_last = timed.last_output
+        timed.last_output = None
+        if rows:
+            y_last = sh.gather(y_last)
+        if rank == 0:
+            dumped = dump_outputs(args.dump_outputs, {"A_x": y_last.cpu().numpy()})
+        del y_last
+
     dist_info = None
     if world > 1:
-        el_local = timed(A_local, x, args.steps, args.warmup)
         dist_info = {"backend": dist.get_backend(), "world_size": dist.get_world_size(),
-                     "layout": args.layout,
-                     "local_matvec_ms": round(1e3 * el_local / args.steps, 4),
-                     "exposed_collective_ms": round(ms_per_step - 1e3 * el_local / args.steps, 4)}
+                     "layout": args.layout}
+    if world > 1 and args.full:
+        # exposed all-reduce: the same K steps of the local matvec alone
+        el_local = timed(A_local, x, args.steps, args.warmup)
+        dist_info.update({"local_matvec_ms": round(1e3 * el_local / args.steps, 4),
+                          "exposed_collective_ms": round(ms_per_step - 1e3 * el_local / args.steps, 4)})
         if rows:
             dist_info.update({"collectives_per_matvec": "all-gather + reduce-scatter of %d rows per rank" % sh.rows,
                               "bytes_sent_per_rank_per_matvec": sh.bytes_per_matvec()})
@@ -610,155 +659,160 @@ def main():
 
     seq_time.last_step_ms = None
     reps = max(5, min(args.steps, 20))
-    stages = {}          # name -> ((mean ms, median ms), bytes_survey, bytes_designed)
-    stage_timing = "each kernel alone, relaunched on its own inputs"
     map_bytes = 48.0 * npix_c
-    tile_info = None
-    if lam:
-        tod = P * x
-        tod2 = N * tod
-        if L._use_tiles(P):
-            T = L._sparse_tiles(P)
-            nv = T.nvalid
-            ang = 8.0 if T.half_angle else 16.0          # half-angle double, or cos and sin
-            st = D.stream
-            d_tb = D.empty(T.nvalid)
-            out = D.empty(n)
-            call = _hip.call
-            tile_info = {"tile_pixels": T.tile_pixels, "tiles": T.ntiles,
-                         "half_angle_storage": T.half_angle,
-                         "pt_order": {0: "atomic", 1: "fixed (time order per pixel, hot runs in fixed chunks, "
-                                      "no atomics)", 2: "exact (time order per pixel)"}[T.pt_mode]}
-            pt_name = "P^T tiles (k_Pt_tiles_fixed)" if T.pt_fixed else "P^T tiles (k_Pt_tiles)"
-            pt_designed = ((8.0 + 4.0 + ang) if T.pt_fixed else (8.0 + 2.0 + ang)) * nv + map_bytes / 2
-            if args.toeplitz == "fused":
-                # the three kernels of a step in sequence, events between them
-                v_tb = D.empty(T.nvalid)
-                p_ms, os_ms, pt_ms = seq_time([
-                    lambda: call("cm2_P_tiles_apply", T.h, D.ptr(x), D.ptr(d_tb), st()),
-                    lambda: call("cm2_noise_apply_tiles", N._noise.h, T.h, D.ptr(d_tb), D.ptr(v_tb), st()),
-                    lambda: call("cm2_Pt_tiles_apply", T.h, D.ptr(v_tb), D.ptr(out), st())], reps)
-                stage_timing = "P, N^-1, P^T launched in sequence, events between the kernels"
-            else:
-                p_ms = ev_time(lambda: call("cm2_P_tiles_apply", T.h, D.ptr(x), D.ptr(d_tb), st()), reps)
-            stages["P tiles (k_P_tiles)"] = (p_ms, 28.0 * nt + map_bytes / 2,
-                                             (2.0 + ang + 8.0) * nv + map_bytes / 2)
-            if args.toeplitz == "fused":
-                kinfo = N.tile_kernel_info()               # which kernel ran, its list format
-                tile_info["overlap_save"] = kinfo
-                os_name = ("k_os_real<%s>, one real window of %d samples per workgroup, %s lists"
-                           % (kinfo["os_kernel"][4:], kinfo["os_window"], kinfo["os_lists"]))
-                stages["N^-1 on tile order (%s)" % os_name] = (
-                    os_ms, 16.0 * nt, float(kinfo["tile_bytes_per_sample"]) * nv)
-                del v_tb
-            else:
-                stages["tiles->time (k_tiles_to_time)"] = (ev_time(lambda: call(
-                    "cm2_tod_tiles_to_time", T.h, D.ptr(d_tb), D.ptr(tod), st()), reps),
-                    16.0 * nt, 22.0 * nt)
-                stages["N^-1 (overlap-save rocFFT)"] = (ev_time(lambda: N * tod, reps), 16.0 * nt,
-                                                        None)
-                stages["time->tiles (k_time_to_tiles)"] = (ev_time(lambda: call(
-                    "cm2_tod_time_to_tiles", T.h, D.ptr(tod2), D.ptr(d_tb), st()), reps),
-                    16.0 * nt, 22.0 * nt)
-            if args.toeplitz != "fused":
-                pt_ms = ev_time(lambda: call("cm2_Pt_tiles_apply", T.h, D.ptr(d_tb), D.ptr(out), st()), reps)
-            stages[pt_name] = (pt_ms, 28.0 * nt + map_bytes / 2, pt_designed)
-            del d_tb, out
-        else:
-            stages["P (k_P_time)"] = (ev_time(lambda: P * x, reps), 28.0 * nt + map_bytes / 2,
-                                      28.0 * nt + map_bytes / 2)
-            stages["N^-1"] = (ev_time(lambda: N * tod, reps), 16.0 * nt, 24.0 * nt)
-            stages["P^T (k_Pt_sell)"] = (ev_time(lambda: P.T * tod2, reps),
-                                         28.0 * nt + map_bytes / 2, 32.0 * nt + map_bytes / 2)
-        step_bytes = 72.0 * nt + map_bytes
-        del tod, tod2
-    else:
-        stages["P^T diag(w) P fused (k_PtNP_sell)"] = (ev_time(lambda: A_local * x, reps),
-                                                       28.0 * nt + map_bytes, 24.0 * nt + map_bytes)
-        step_bytes = 28.0 * nt + map_bytes
-    dom = max(stages, key=lambda k: stages[k][0][0])
-    (dom_mean, dom_med), dom_bytes, dom_designed = stages[dom]
-    # One consistent set of times.  The K timed steps run WITHOUT events between the kernels
-    # (ms_per_step); the stage times come from the same three launches with an event between every
-    # two, and add up to the step measured between the same events (`step_ms_same_events`, equal to the
-    # sum by construction).  An event between two kernels keeps the command processor from fetching the
-    # next dispatch while the previous kernel drains: `event_gap_ms` = (step with events - step without)
-    # / kernels is what each event interval contains beside its kernel, and `avg_launch_ms` -- the
-    # figure rocprofv3's average duration of the same kernel is to be compared with -- is the interval
-    # minus that gap (`avg_launch_ms_event_interval` is the raw interval).
-    timing = {"kind": stage_timing}
-    gap = 0.0
-    if seq_time.last_step_ms is not None and world == 1:
-        nk = len(stages)
-        ssum = sum(v[0][0] for v in stages.values())
-        gap = max(0.0, (seq_time.last_step_ms - ms_per_step) / nk)
-        timing.update({"stages_sum_ms": round(ssum, 4), "step_ms_same_events": round(seq_time.last_step_ms, 4),
-                       "step_ms_no_events": round(ms_per_step, 4), "event_gap_ms": round(gap, 4),
-                       "stages_sum_minus_gaps_ms": round(ssum - nk * gap, 4)})
-    dom_net = dom_mean - gap
-    achieved = dom_bytes / (dom_net * 1e-3) / 1e9
-    roofline = {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 1),
-                "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
-                "traffic": None, "traffic_measured_in_run": False,
-                "algorithmic_bytes": dom_bytes, "designed_bytes": dom_designed,
-                "avg_launch_ms": round(dom_net, 4), "avg_launch_ms_event_interval": round(dom_mean, 4)}
-    # HBM traffic of the dominant kernel from the PMC counters.  FETCH_SIZE / WRITE_SIZE need
-    # rocprofv3 passes of their own, so the figure is NOT measured in this run: it is copied from
-    # the newest committed summary of this command (profiles/make_summary.py), only when workload
-    # and size are the same, and labelled with that profile's file and commit.
-    if traffic_pre is not None:
-        # measured by this run (the two rocprofv3 --pmc children at the top of main), if they profiled the kernel
-        # that turned out to be the dominant one
-        if "error" in traffic_pre:
-            roofline["traffic_measurement_error"] = traffic_pre["error"]
-        elif traffic_pre["regex"] in dom:
-            passes = traffic_pre["passes"]
-            roofline.update({"traffic": traffic_pre["traffic"], "traffic_measured_in_run": True,
-                             "traffic_passes": {"FETCH_SIZE_bytes": passes["FETCH_SIZE"]["bytes"],
-                                                "WRITE_SIZE_bytes": passes["WRITE_SIZE"]["bytes"],
-                                                "launches_per_pass": passes["FETCH_SIZE"]["launches"],
-                                                "formula": "2 * FETCH_SIZE + WRITE_SIZE (gfx950: FETCH_SIZE counts "
-                                                           "128-byte requests at 64 bytes)",
-                                                "how": "two child processes of bench.py under rocprofv3 --pmc, started "
-                                                       "before this process touched the GPU",
-                                                "seconds": traffic_pre["seconds"]}})
-        else:
-            roofline["traffic_measurement_error"] = "profiled %s, dominant kernel is %s" % (traffic_pre["regex"], dom)
-    if roofline["traffic"] is None:
-        try:
-            pmcs = sorted(f for f in os.listdir(os.path.join(ROOT, "profiles")) if f.endswith("_pmc_c4.json"))
-            pmc = json.load(open(os.path.join(ROOT, "profiles", pmcs[-1])))
-            if pmc["workload"] == cfg["label"] and pmc["nt_per_gpu"] == nt:
-                for kname, rec in pmc["kernels"].items():
-                    if kname in dom and rec.get("hbm_traffic_bytes"):
-                        roofline["traffic"] = rec["hbm_traffic_bytes"]
-                        roofline["traffic_source"] = "profiles/" + pmcs[-1]
-                        roofline["traffic_source_commit"] = pmc.get("commit")
-                        roofline["traffic_source_sources_sha16"] = pmc.get("library_sources_sha16")
-        except Exception:
-            pass
+    step_bytes = (72.0 if lam else 28.0) * nt + map_bytes      # SURVEY 8(d) bytes of one step
     step_gbs = step_bytes / (ms_per_step * 1e-3) / 1e9
-    stage_report = {}
-    for k, v in stages.items():
-        ms = v[0][0]
-        rec = {"ms": round(ms, 4), "bytes_survey": v[1]}
-        if v[2] is None or v[2] >= v[1]:
-            # a rate on SURVEY's algorithmic bytes is only a bandwidth when the kernel moves at
-            # least that much: k_P_tiles / k_Pt_tiles are built to move fewer bytes than SURVEY
-            # counts (half-angle storage), and bytes_survey / time there is a throughput figure
-            # that can exceed the HBM peak -- it is reported as samples/s only
-            rec["GB/s_survey"] = round(v[1] / (ms * 1e-3) / 1e9, 1)
+    # the tile plan the timed operator ran on (a description of the plan built during the setup)
+    tile_info = None
+    if lam and L._use_tiles(P):
+        T = L._sparse_tiles(P)
+        tile_info = {"tile_pixels": T.tile_pixels, "tiles": T.ntiles,
+                     "half_angle_storage": T.half_angle,
+                     "pt_order": {0: "atomic", 1: "fixed (time order per pixel, hot runs in fixed chunks, "
+                                  "no atomics)", 2: "exact (time order per pixel)"}[T.pt_mode]}
+        if args.toeplitz == "fused":
+            tile_info["overlap_save"] = N.tile_kernel_info()       # which kernel ran, its list format
+    stage_report = timing = roofline = None
+    if args.full:
+        stages = {}          # name -> ((mean ms, median ms), bytes_survey, bytes_designed)
+        stage_timing = "each kernel alone, relaunched on its own inputs"
+        if lam:
+            tod = P * x
+            tod2 = N * tod
+            if L._use_tiles(P):
+                T = L._sparse_tiles(P)
+                nv = T.nvalid
+                ang = 8.0 if T.half_angle else 16.0          # half-angle double, or cos and sin
+                st = D.stream
+                d_tb = D.empty(T.nvalid)
+                out = D.empty(n)
+                call = _hip.call
+                pt_name = "P^T tiles (k_Pt_tiles_fixed)" if T.pt_fixed else "P^T tiles (k_Pt_tiles)"
+                pt_designed = ((8.0 + 4.0 + ang) if T.pt_fixed else (8.0 + 2.0 + ang)) * nv + map_bytes / 2
+                if args.toeplitz == "fused":
+                    # the three kernels of a step in sequence, events between them
+                    v_tb = D.empty(T.nvalid)
+                    p_ms, os_ms, pt_ms = seq_time([
+                        lambda: call("cm2_P_tiles_apply", T.h, D.ptr(x), D.ptr(d_tb), st()),
+                        lambda: call("cm2_noise_apply_tiles", N._noise.h, T.h, D.ptr(d_tb), D.ptr(v_tb), st()),
+                        lambda: call("cm2_Pt_tiles_apply", T.h, D.ptr(v_tb), D.ptr(out), st())], reps)
+                    stage_timing = "P, N^-1, P^T launched in sequence, events between the kernels"
+                else:
+                    p_ms = ev_time(lambda: call("cm2_P_tiles_apply", T.h, D.ptr(x), D.ptr(d_tb), st()), reps)
+                stages["P tiles (k_P_tiles)"] = (p_ms, 28.0 * nt + map_bytes / 2,
+                                                 (2.0 + ang + 8.0) * nv + map_bytes / 2)
+                if args.toeplitz == "fused":
+                    kinfo = tile_info["overlap_save"]
+                    os_name = ("k_os_real<%s>, one real window of %d samples per workgroup, %s lists"
+                               % (kinfo["os_kernel"][4:], kinfo["os_window"], kinfo["os_lists"]))
+                    stages["N^-1 on tile order (%s)" % os_name] = (
+                        os_ms, 16.0 * nt, float(kinfo["tile_bytes_per_sample"]) * nv)
+                    del v_tb
+                else:
+                    stages["tiles->time (k_tiles_to_time)"] = (ev_time(lambda: call(
+                        "cm2_tod_tiles_to_time", T.h, D.ptr(d_tb), D.ptr(tod), st()), reps),
+                        16.0 * nt, 22.0 * nt)
+                    stages["N^-1 (overlap-save rocFFT)"] = (ev_time(lambda: N * tod, reps), 16.0 * nt,
+                                                            None)
+                    stages["time->tiles (k_time_to_tiles)"] = (ev_time(lambda: call(
+                        "cm2_tod_time_to_tiles", T.h, D.ptr(tod2), D.ptr(d_tb), st()), reps),
+                        16.0 * nt, 22.0 * nt)
+                if args.toeplitz != "fused":
+                    pt_ms = ev_time(lambda: call("cm2_Pt_tiles_apply", T.h, D.ptr(d_tb), D.ptr(out), st()), reps)
+                stages[pt_name] = (pt_ms, 28.0 * nt + map_bytes / 2, pt_designed)
+                del d_tb, out
+            else:
+                stages["P (k_P_time)"] = (ev_time(lambda: P * x, reps), 28.0 * nt + map_bytes / 2,
+                                          28.0 * nt + map_bytes / 2)
+                stages["N^-1"] = (ev_time(lambda: N * tod, reps), 16.0 * nt, 24.0 * nt)
+                stages["P^T (k_Pt_sell)"] = (ev_time(lambda: P.T * tod2, reps),
+                                             28.0 * nt + map_bytes / 2, 32.0 * nt + map_bytes / 2)
+            del tod, tod2
         else:
-            rec["samples_per_s"] = round(nt / (ms * 1e-3), 1)
-        if v[2] is not None:
-            rec["bytes_designed"] = v[2]
-            rec["GB/s_designed"] = round(v[2] / (ms * 1e-3) / 1e9, 1)
-            rec["frac_of_hbm_peak_designed"] = round(v[2] / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
-        stage_report[k] = rec
+            stages["P^T diag(w) P fused (k_PtNP_sell)"] = (ev_time(lambda: A_local * x, reps),
+                                                           28.0 * nt + map_bytes, 24.0 * nt + map_bytes)
+        dom = max(stages, key=lambda k: stages[k][0][0])
+        (dom_mean, dom_med), dom_bytes, dom_designed = stages[dom]
+        # One consistent set of times.  The K timed steps run WITHOUT events between the kernels
+        # (ms_per_step); the stage times come from the same three launches with an event between every
+        # two, and add up to the step measured between the same events (`step_ms_same_events`, equal to the
+        # sum by construction).  An event between two kernels keeps the command processor from fetching the
+        # next dispatch while the previous kernel drains: `event_gap_ms` = (step with events - step without)
+        # / kernels is what each event interval contains beside its kernel, and `avg_launch_ms` -- the
+        # figure rocprofv3's average duration of the same kernel is to be compared with -- is the interval
+        # minus that gap (`avg_launch_ms_event_interval` is the raw interval).
+        timing = {"kind": stage_timing}
+        gap = 0.0
+        if seq_time.last_step_ms is not None and world == 1:
+            nk = len(stages)
+            ssum = sum(v[0][0] for v in stages.values())
+            gap = max(0.0, (seq_time.last_step_ms - ms_per_step) / nk)
+            timing.update({"stages_sum_ms": round(ssum, 4), "step_ms_same_events": round(seq_time.last_step_ms, 4),
+                           "step_ms_no_events": round(ms_per_step, 4), "event_gap_ms": round(gap, 4),
+                           "stages_sum_minus_gaps_ms": round(ssum - nk * gap, 4)})
+        dom_net = dom_mean - gap
+        achieved = dom_bytes / (dom_net * 1e-3) / 1e9
+        roofline = {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 1),
+                    "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
+                    "traffic": None, "traffic_measured_in_run": False,
+                    "algorithmic_bytes": dom_bytes, "designed_bytes": dom_designed,
+                    "avg_launch_ms": round(dom_net, 4), "avg_launch_ms_event_interval": round(dom_mean, 4)}
+        # HBM traffic of the dominant kernel from the PMC counters.  FETCH_SIZE / WRITE_SIZE need
+        # rocprofv3 passes of their own, so the figure is NOT measured in this run: it is copied from
+        # the newest committed summary of this command (profiles/make_summary.py), only when workload
+        # and size are the same, and labelled with that profile's file and commit.
+        if traffic_pre is not None:
+            # measured by this run (the two rocprofv3 --pmc children at the top of main), if they profiled the kernel
+            # that turned out to be the dominant one
+            if "error" in traffic_pre:
+                roofline["traffic_measurement_error"] = traffic_pre["error"]
+            elif traffic_pre["regex"] in dom:
+                passes = traffic_pre["passes"]
+                roofline.update({"traffic": traffic_pre["traffic"], "traffic_measured_in_run": True,
+                                 "traffic_passes": {"FETCH_SIZE_bytes": passes["FETCH_SIZE"]["bytes"],
+                                                    "WRITE_SIZE_bytes": passes["WRITE_SIZE"]["bytes"],
+                                                    "launches_per_pass": passes["FETCH_SIZE"]["launches"],
+                                                    "formula": "2 * FETCH_SIZE + WRITE_SIZE (gfx950: FETCH_SIZE counts "
+                                                               "128-byte requests at 64 bytes)",
+                                                    "how": "two child processes of bench.py under rocprofv3 --pmc, started "
+                                                           "before this process touched the GPU",
+                                                    "seconds": traffic_pre["seconds"]}})
+            else:
+                roofline["traffic_measurement_error"] = "profiled %s, dominant kernel is %s" % (traffic_pre["regex"], dom)
+        if roofline["traffic"] is None:
+            try:
+                pmcs = sorted(f for f in os.listdir(os.path.join(ROOT, "profiles")) if f.endswith("_pmc_c4.json"))
+                pmc = json.load(open(os.path.join(ROOT, "profiles", pmcs[-1])))
+                if pmc["workload"] == cfg["label"] and pmc["nt_per_gpu"] == nt:
+                    for kname, rec in pmc["kernels"].items():
+                        if kname in dom and rec.get("hbm_traffic_bytes"):
+                            roofline["traffic"] = rec["hbm_traffic_bytes"]
+                            roofline["traffic_source"] = "profiles/" + pmcs[-1]
+                            roofline["traffic_source_commit"] = pmc.get("commit")
+                            roofline["traffic_source_sources_sha16"] = pmc.get("library_sources_sha16")
+            except Exception:
+                pass
+        stage_report = {}
+        for k, v in stages.items():
+            ms = v[0][0]
+            rec = {"ms": round(ms, 4), "bytes_survey": v[1]}
+            if v[2] is None or v[2] >= v[1]:
+                # a rate on SURVEY's algorithmic bytes is only a bandwidth when the kernel moves at
+                # least that much: k_P_tiles / k_Pt_tiles are built to move fewer bytes than SURVEY
+                # counts (half-angle storage), and bytes_survey / time there is a throughput figure
+                # that can exceed the HBM peak -- it is reported as samples/s only
+                rec["GB/s_survey"] = round(v[1] / (ms * 1e-3) / 1e9, 1)
+            else:
+                rec["samples_per_s"] = round(nt / (ms * 1e-3), 1)
+            if v[2] is not None:
+                rec["bytes_designed"] = v[2]
+                rec["GB/s_designed"] = round(v[2] / (ms * 1e-3) / 1e9, 1)
+                rec["frac_of_hbm_peak_designed"] = round(v[2] / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
+            stage_report[k] = rec
 
     # ---- PCG iterations to 1e-6 (outside the timed region) ----------------------------
     pcg = None
-    if not args.no_pcg and rows:
+    if args.full and not args.no_pcg and rows:
         # PCG on row-sharded vectors: M_BD and the two-level preconditioner act on this rank's rows, the
         # three dot products of an iteration are 8-byte all-reduces, Z^T r an r-vector all-reduce
         from cosmomap2_amd.interfaces import ritz_deflation_basis
@@ -799,7 +853,7 @@ def main():
                                     (sh.gather(xs2) - sh.gather(xs)).norm() / sh.gather(xs).norm())}
             del Zl, AZl, M2, xs2
         del b_loc, xs, Mr
-    elif not args.no_pcg:
+    elif args.full and not args.no_pcg:
         b = P.T * (N * d)
         if world > 1:
             dist.all_reduce(b)
@@ -927,7 +981,7 @@ def main():
 
     # ---- 8(f) rows: sub-scan and ground filters on the same TOD (rank 0, untimed extras) ----
     filters = None
-    if rank == 0 and world == 1 and not args.no_filters:
+    if args.full and rank == 0 and world == 1 and not args.no_filters:
         from cosmomap2_amd.interfaces import FilterLO, GroundFilterLO
         sub, gap = 2000, 40                       # sub-scan and turnaround lengths (samples)
         starts = np.arange(0, bsize - sub + 1, sub + gap)
@@ -979,7 +1033,7 @@ def main():
     raster = None
     # (the secondary pointing models build a second and a third pointing plan beside the first: at more than
     #  2.5e8 samples on one GPU -- C5 whole -- they are skipped, 1e9 samples x 3 plans do not fit 288 GB)
-    secondary = rank == 0 and world == 1 and lam and not args.no_raster and nt <= 250_000_000
+    secondary = args.full and rank == 0 and world == 1 and lam and not args.no_raster and nt <= 250_000_000
     if secondary and npix % 1024 == 0:
         Wc, dwell = 1024, 4
         Hr = npix // Wc
@@ -1086,7 +1140,7 @@ def main():
 
     # ---- the other scaling mode's point (N > 1) --------------------------------------------
     other = None
-    if world > 1 and not args.no_other_point:
+    if args.full and world > 1 and not args.no_other_point:
         other_mode = "strong" if args.scaling == "weak" else "weak"
         del A, A_local, P, N, Mbd, ces, x, d, pix, S
         torch.cuda.empty_cache()
@@ -1104,7 +1158,7 @@ def main():
 
     # ---- CPU baseline: the oracle (1 core, reference-unfused) on a bounded sample -----
     cpu = cpu_all = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         from oracle import oracle as orc
         orc.build()
         ns = min(nt, 1_000_000 if lam else 20_000_000)
@@ -1171,7 +1225,7 @@ def main():
     # M_BD, all host threads for P / N^-1 / P^T).  north_star: maps within 1e-6 relative l2,
     # identical iteration counts.
     parity = None
-    if rank == 0 and world == 1 and not args.no_parity and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_parity and not args.no_cpu:
         from oracle import oracle as orc
         tq = time.perf_counter()
         beat = Heartbeat("parity_full_size: the oracle on the host")
@@ -1290,17 +1344,20 @@ def main():
 
     # device memory at the end of the run: what the library's objects hold, what it keeps cached, and
     # torch's peak (the vectors of the solves and the TOD-sized scratch of the operator)
-    mem = (ctypes.c_int64 * 4)()
-    _hip.call("cm2_device_memory_info", mem)
-    memory = {"library_live_GB": round(mem[0] / 1e9, 3), "library_cached_GB": round(mem[1] / 1e9, 3),
-              "torch_peak_allocated_GB": round(torch.cuda.max_memory_allocated() / 1e9, 3),
-              "computed_budget_per_rank_strong_scaling_GB": strong_budget()}
+    memory = None
+    if args.full:
+        mem = (ctypes.c_int64 * 4)()
+        _hip.call("cm2_device_memory_info", mem)
+        memory = {"library_live_GB": round(mem[0] / 1e9, 3), "library_cached_GB": round(mem[1] / 1e9, 3),
+                  "torch_peak_allocated_GB": round(torch.cuda.max_memory_allocated() / 1e9, 3),
+                  "computed_budget_per_rank_strong_scaling_GB": strong_budget()}
     if rank == 0:
         out = {
             "metric": "TOD samples/s through P^T N^-1 P",
             "value": value, "unit": "TOD samples/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
             "scaling": args.scaling, "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "full": bool(args.full), "dumped_outputs": dumped,
             "config": {"workload": cfg["label"], "nside": cfg["nside"], "pol": pol,
                        "nt_per_gpu": nt, "nt_all_gpus": nt_all, "npix": int(npix_c),
                        "noise": ("toeplitz" if lam else "diag"),
@@ -1322,7 +1379,7 @@ def main():
             "cpu_baseline": cpu,
             "cpu_baseline_all_cores": cpu_all,
             "hbm_memory": memory,
-            "device_state": device_state(),
+            "device_state": device_state() if args.full else None,
             "library": library_stamp(),
             "setup_seconds": round(t_setup, 2),
             "setup_split_seconds": {k: round(v, 3) for k, v in S_setup.items()},

@@ -8,7 +8,7 @@ Expects (all produced on the MI355X box, see the command block written into the 
   <dir>/kt/**/_kernel_stats.csv          rocprofv3 --kernel-trace --stats
   <dir>/fetch/**/_counter_collection.csv rocprofv3 --pmc FETCH_SIZE   (own pass)
   <dir>/write/**/_counter_collection.csv rocprofv3 --pmc WRITE_SIZE   (own pass)
-  <dir>/bench_default.json               un-profiled `python3 bench.py`
+  <dir>/bench_default.json               un-profiled `python3 bench.py --full`
 Writes profiles/<tag>_bench_c4.json, <tag>_rocprofv3_kernel_stats_c4.csv, <tag>_pmc_c4.json/.md.
 FETCH_SIZE / WRITE_SIZE are KiB per dispatch; on gfx950 FETCH_SIZE counts half the bytes of a
 wide coalesced read (MI355X_MICROARCH.md, HBM section), so HBM traffic = 2*FETCH + WRITE.
@@ -105,11 +105,11 @@ def main(src, tag):
                    "correction); separate --pmc passes"}
     json.dump(out, open(os.path.join(here, tag + "_pmc_c4.json"), "w"), indent=1)
 
-    md = ["# rocprofv3 summary %s -- `python3 bench.py` (%s)" % (tag, bench["config"]["workload"]), "",
+    md = ["# rocprofv3 summary %s -- `python3 bench.py --full` (%s)" % (tag, bench["config"]["workload"]), "",
           "Commands (MI355X box, after `cd /tmp && export TMPDIR=/tmp`):", "",
-          "    rocprofv3 --kernel-trace --stats -d out/kt --output-format csv -- python3 bench.py --steps 20 --warmup 3 --no-cpu --no-filters --no-raster",
-          "    rocprofv3 --pmc FETCH_SIZE --kernel-trace -d out/fetch --output-format csv -- python3 bench.py --steps 3 --warmup 1 --no-cpu --no-filters --no-raster --arnoldi-steps 40",
-          "    rocprofv3 --pmc WRITE_SIZE --kernel-trace -d out/write --output-format csv -- python3 bench.py --steps 3 --warmup 1 --no-cpu --no-filters --no-raster --arnoldi-steps 40",
+          "    rocprofv3 --kernel-trace --stats -d out/kt --output-format csv -- python3 bench.py --full --steps 20 --warmup 3 --no-cpu --no-filters --no-raster",
+          "    rocprofv3 --pmc FETCH_SIZE --kernel-trace -d out/fetch --output-format csv -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu --no-filters --no-raster --arnoldi-steps 40",
+          "    rocprofv3 --pmc WRITE_SIZE --kernel-trace -d out/write --output-format csv -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu --no-filters --no-raster --arnoldi-steps 40",
           "", "Full kernel table: `%s_rocprofv3_kernel_stats_c4.csv`; machine-readable: `%s_pmc_c4.json`." % (tag, tag),
           "", "| kernel | calls | avg ms (rocprofv3) | 2*FETCH_SIZE GB | WRITE_SIZE GB | HBM traffic GB | GB/s of HBM traffic | algorithmic GB | GB/s algorithmic |",
           "|---|---|---|---|---|---|---|---|---|"]

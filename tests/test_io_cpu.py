@@ -231,7 +231,7 @@ def test_ritz_checkpoint_and_map_lists(U, tmp_path):
 
 
 # ------------------------------------------------------------------ HEALPix FITS -----
-REF_FITS = "/root/reference/data/cmb_r0.2_3.5arcmin_128.fits"
+REF_FITS = os.path.join(GOLD, "reference_cmb_map_head.fits")
 
 
 def test_healpix_fits_write_read_round_trip(tmp_path):
@@ -354,10 +354,11 @@ def test_ring_nested_reordering_against_pixel_geometry(nside):
 
 def test_healpix_fits_reader_on_the_reference_map():
     """The reference's input map data/cmb_r0.2_3.5arcmin_128.fits (synfast, 3 x 1024E columns)
-    through read_map, against pixel samples and sums taken from the file by
-    tests/golden/make_fits_fixture.py.  The 2.3 MB file itself is not committed: the test runs
-    where the reference tree exists (the build container) and is skipped elsewhere; the
-    committed header cards are checked against the parser everywhere."""
+    through read_map.  The 2.3 MB file itself is not committed; tests/golden/make_fits_fixture.py
+    stores its header cards, pixel samples and sums, and reference_cmb_map_head.fits: the file's own
+    bytes cut to its first 12 table rows (nside 32; only NAXIS2, NSIDE and LASTPIX rewritten).  The
+    full header cards are checked against the parser, the cut file against a separate NumPy view of
+    its table, against the samples that fall in it and against the sums of its rows."""
     from cosmomap2_amd.utilities import healpix_fits as hf
     G = np.load(os.path.join(GOLD, "reference_cmb_map_samples.npz"))
     cards = [bytes(row).decode("ascii") for row in G["header_cards"]]
@@ -367,15 +368,27 @@ def test_healpix_fits_reader_on_the_reference_map():
     assert hdr["XTENSION"] == "BINTABLE" and hdr["NAXIS1"] == 12288 and hdr["NAXIS2"] == 192
     assert hdr["TFORM1"] == "1024E" and hdr["NSIDE"] == 128 and hdr["ORDERING"] == "RING"
     assert hdr["POLAR"] is True and abs(hdr["BAD_DATA"] + 1.6375e30) < 1e18
-    if not os.path.exists(REF_FITS):
-        pytest.skip("reference tree not present")
-    I, Q, U = hf.read_map(REF_FITS, field=[0, 1, 2])
+    rows = int(G["head_rows"])
+    npix = rows * 1024
+    I, Q, U, h = hf.read_map(REF_FITS, field=[0, 1, 2], h=True)
+    assert I.shape == Q.shape == U.shape == (npix,) and I.dtype == np.float64
+    assert h["NSIDE"] == 32 and 12 * h["NSIDE"] ** 2 == npix and h["LASTPIX"] == npix - 1
+    # every header card of the cut file but the three size cards is the reference's
+    assert {k: v for k, v in h.items() if k not in ("NAXIS2", "NSIDE", "LASTPIX")} == \
+        {k: v for k, v in hdr.items() if k in h and k not in ("NAXIS2", "NSIDE", "LASTPIX")}
+    data = open(REF_FITS, "rb").read()
+    table = np.frombuffer(data, dtype=">f4", count=rows * 3 * 1024,
+                          offset=int(G["header_bytes"])).reshape(rows, 3, 1024)
+    for i, m in enumerate((I, Q, U)):
+        np.testing.assert_array_equal(m, table[:, i, :].reshape(-1).astype(np.float64))
     pix = G["pixels"]
-    np.testing.assert_array_equal(I[pix], G["I"])
-    np.testing.assert_array_equal(Q[pix], G["Q"])
-    np.testing.assert_array_equal(U[pix], G["U"])
-    np.testing.assert_allclose([I.sum(), Q.sum(), U.sum()], G["sums"], rtol=1e-12)
-    np.testing.assert_allclose([(I * I).sum(), (Q * Q).sum(), (U * U).sum()], G["sumsq"], rtol=1e-12)
+    sel = pix < npix
+    assert sel.sum() > 200
+    np.testing.assert_array_equal(I[pix[sel]], G["I"][sel])
+    np.testing.assert_array_equal(Q[pix[sel]], G["Q"][sel])
+    np.testing.assert_array_equal(U[pix[sel]], G["U"][sel])
+    np.testing.assert_allclose([I.sum(), Q.sum(), U.sum()], G["head_sums"], rtol=1e-12)
+    np.testing.assert_allclose([(I * I).sum(), (Q * Q).sum(), (U * U).sum()], G["head_sumsq"], rtol=1e-12)
     np.testing.assert_array_equal(hf.read_map(REF_FITS), I)
 
 
