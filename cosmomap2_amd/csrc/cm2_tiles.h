@@ -15,12 +15,9 @@ struct cm2_tiles {
     std::vector<int64_t> tile_p0;   // [ntiles+1] first pixel of every tile (host)
     int64_t *d_tile_p0 = nullptr;
     int64_t ntiles = 0, nitems = 0;
-    // The tables below keep the general [span][tile][time] form of round 4's span order with ONE span (the
-    // global tile order; the option itself was measured out and removed in round 5, cm2_tiles.hip): segment
-    // (0, tile b) = the tile's whole bucket, addresses [seg_off[b], seg_off[b + 1]).
-    int64_t nspans = 1, span_samples = 0;
-    std::vector<int64_t> seg_off;   // [nspans * ntiles + 1] (host)
-    int64_t *d_seg_off = nullptr;
+    // tile b's bucket = the addresses [tile_off[b], tile_off[b + 1])
+    std::vector<int64_t> tile_off;  // [ntiles+1] first address of every tile (host)
+    int64_t *d_tile_off = nullptr;
     uint32_t *d_tb_dst = nullptr;   // [nt]
     uint16_t *d_pl = nullptr;       // [nvalid]
     double *d_cos = nullptr, *d_sin = nullptr;   // [nvalid]  (full-angle mode)
@@ -30,10 +27,9 @@ struct cm2_tiles {
     // sample in each of the two tile kernels
     bool half = false;
     double *d_half = nullptr;                    // [nvalid]
-    // work items of k_P_tiles / k_Pt_tiles: tile, spans [sp0, sp1) of it, clipped to the addresses
-    // [k0, k1) (a segment longer than the slice length is cut into several items)
+    // work items of k_P_tiles / k_Pt_tiles: tile and the addresses [k0, k1) of its bucket (a bucket
+    // longer than the slice length is cut into several items)
     int32_t *d_item_tile = nullptr; // [nitems]
-    int2 *d_item_span = nullptr;    // [nitems] {sp0, sp1}
     int64_t *d_item_k0 = nullptr;   // [nitems]
     int64_t *d_item_k1 = nullptr;
     std::vector<int64_t> tile_item0;   // [ntiles+1] first work item of every tile (host)

@@ -131,18 +131,9 @@ __global__ __launch_bounds__(256) void k_tile_bounds(const uint32_t *__restrict_
 constexpr int kSplitChunk = 8192;                        // samples per wave (rank fits 16 bits)
 constexpr int64_t kSplitMaxTiles = 8192;                 // 4 wave histograms of u16 in 64 KB of LDS
 
-// SPANS.  The counts are stored [span][tile][chunk of the span] (G chunks a span, the last span padded
-// with empty chunks): the same exclusive scan then yields the order [span][tile][time] -- every span
-// of G x 8192 consecutive time samples is partitioned by tile on its own, and segment (span, tile)
-// starts at base[(span * ntiles + tile) * G].  G = number of chunks (one span) is the global tile order.
-__host__ __device__ inline int64_t cnt_index(int64_t tile, int64_t chunk, int64_t ntiles, int64_t G)
-{
-    return ((chunk / G) * ntiles + tile) * G + chunk % G;
-}
-
 __global__ __launch_bounds__(256) void k_tile_rank(const int32_t *__restrict__ pix, int64_t nt, int tp,
                                                     const int64_t *__restrict__ p0, uint32_t ntiles,
-                                                    int64_t npix, int64_t nchunks, int64_t G,
+                                                    int64_t npix, int64_t nchunks,
                                                     uint32_t *__restrict__ packed,
                                                     uint32_t *__restrict__ cnt_t,
                                                     unsigned int *__restrict__ bad)
@@ -178,27 +169,27 @@ __global__ __launch_bounds__(256) void k_tile_rank(const int32_t *__restrict__ p
             packed[idx] = 0xFFFFFFFFu;
         }
     }
-    for (uint32_t b = lane; b < ntiles; b += 64) cnt_t[cnt_index(b, c, ntiles, G)] = hist[b];
+    for (uint32_t b = lane; b < ntiles; b += 64) cnt_t[b * nchunks + c] = hist[b];
     if (b_) atomicOr(bad, 1u);
 }
 
-// off[s] = first address of segment s = span * ntiles + tile (s <= nsegs: the last one is the number of
-// valid samples)
-__global__ __launch_bounds__(256) void k_tile_offsets(const uint32_t *__restrict__ base, int64_t G,
-                                                       int64_t nsegs, int64_t *__restrict__ off)
+// off[b] = first address of tile b (b <= ntiles: the last one is the number of valid samples)
+__global__ __launch_bounds__(256) void k_tile_offsets(const uint32_t *__restrict__ base, int64_t nchunks,
+                                                       int64_t ntiles, int64_t *__restrict__ off)
 {
-    const int64_t sg = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (sg <= nsegs) off[sg] = base[sg * G];
+    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b <= ntiles) off[b] = base[b * nchunks];
 }
 
 template <int POL, bool HALF>
 __global__ __launch_bounds__(256) void k_tile_place(
-    int64_t nt, int tp, const int64_t *__restrict__ p0, int64_t ntiles, int64_t G,
+    int64_t nt, int tp, const int64_t *__restrict__ p0,
     const uint32_t *__restrict__ packed, const uint32_t *__restrict__ base,
     const int32_t *__restrict__ pix, const double *__restrict__ c, const double *__restrict__ s,
     uint32_t *__restrict__ tb_dst, uint16_t *__restrict__ pl, double *__restrict__ ctb,
     double *__restrict__ stb)
 {
+    const int64_t nchunks = (nt + kSplitChunk - 1) / kSplitChunk;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nt; i += stride) {
         const uint32_t pk = packed[i];
@@ -207,7 +198,7 @@ __global__ __launch_bounds__(256) void k_tile_place(
             continue;
         }
         const int64_t tile = pk >> 16;
-        const uint32_t k = base[cnt_index(tile, i / kSplitChunk, ntiles, G)] + (pk & 0xFFFFu);
+        const uint32_t k = base[tile * nchunks + i / kSplitChunk] + (pk & 0xFFFFu);
         tb_dst[i] = k;
         const int32_t px = pix[i];
         uint16_t w = p0 ? (uint16_t)(px - p0[tile]) : (uint16_t)(px - (int32_t)tile * tp);
@@ -237,7 +228,7 @@ __global__ __launch_bounds__(256) void k_tile_place(
 // one-array forms (pol = 1, half angles): 8192 doubles + 2 x 8192 words + two tables per tile.
 template <int POL>
 __global__ __launch_bounds__(256) void k_tile_place_staged(
-    int64_t nt, int tp, const int64_t *__restrict__ p0, int64_t G, int ntiles,
+    int64_t nt, int tp, const int64_t *__restrict__ p0, int ntiles,
     const uint32_t *__restrict__ packed, const uint32_t *__restrict__ base,
     const int32_t *__restrict__ pix, const double *__restrict__ c, const double *__restrict__ s,
     uint32_t *__restrict__ tb_dst, uint16_t *__restrict__ pl, double *__restrict__ ctb)
@@ -249,14 +240,14 @@ __global__ __launch_bounds__(256) void k_tile_place_staged(
     uint16_t *ws = reinterpret_cast<uint16_t *>(lbase + ntiles + 1);   // [kSplitChunk] pl words by slot
     uint16_t *ts = ws + kSplitChunk;                                // [kSplitChunk] tile of the slot
     __shared__ uint32_t wsum[4];
-    const int64_t ch = blockIdx.x;
+    const int64_t ch = blockIdx.x, nchunks = gridDim.x;
     const int64_t i0 = ch * kSplitChunk, i1 = i0 + kSplitChunk < nt ? i0 + kSplitChunk : nt;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     // per-tile counts of the chunk (next word of the tile-major scan minus this one), scanned
     const int per = (ntiles + 255) / 256;
     uint32_t mine = 0;
     for (int b = t * per; b < (t + 1) * per && b < ntiles; ++b) {
-        const int64_t ci = cnt_index(b, ch, ntiles, G);
+        const int64_t ci = b * nchunks + ch;
         const uint32_t g0 = base[ci], g1 = base[ci + 1];
         gbase[b] = g0;
         lbase[b] = g1 - g0;
@@ -407,16 +398,16 @@ __device__ __forceinline__ void tile_sample(const uint16_t *__restrict__ pl,
     }
 }
 
-constexpr int kSegBatch = 128;           // segments of a work item whose bounds are staged in LDS at a time
+// workgroup size of the two tile kernels: 1024 threads for the gather (0.355 vs 0.38 ms at
+// 1e8 samples), 512 for the scatter (no difference)
+constexpr int kPBlock = 1024, kPtBlock = 512;
 
 // ------------------------------------------------------------------ P (TB) ------
-// one workgroup per work item = (tile, spans [sp0, sp1) of its samples, clipped to the addresses
-// [k0, k1)): the tile of x is staged once, the item's segments (one per span, ~2000 consecutive
-// addresses each; the whole bucket when the plan has one span) are streamed one after the other
+// one workgroup per work item = (tile, addresses [k0, k1) of its bucket): the tile of x is staged
+// once, the item's samples are streamed
 template <int POL, bool HALF>
 __global__ __launch_bounds__(1024) void k_P_tiles(
     const int64_t *__restrict__ tile_p0, const int32_t *__restrict__ item_tile,
-    const int2 *__restrict__ item_span, const int64_t *__restrict__ seg_off, int64_t ntiles,
     const int64_t *__restrict__ item_k0, const int64_t *__restrict__ item_k1,
     const uint16_t *__restrict__ pl, const double *__restrict__ c, const double *__restrict__ s,
     const double *__restrict__ x, double *__restrict__ d_tb)
@@ -429,74 +420,29 @@ __global__ __launch_bounds__(1024) void k_P_tiles(
     const double *xs = x + p0 * POL;
     for (int64_t i = threadIdx.x; i < nvals; i += blockDim.x) tile[i] = xs[i];
     __syncthreads();
-    // The item's segments as ONE index space: their bounds are fetched together (a dependent load per
-    // segment in front of its samples cost 12 % at C4, and a raster scan -- most segments of a tile
-    // empty -- 10 %), scanned in LDS, and sample j of the item is sample j - pre[i] of segment i: no
-    // partly filled pass at the end of every segment.  Batches of kSegBatch segments.
-    __shared__ int64_t seg_k0[kSegBatch];
-    __shared__ uint32_t seg_pre[kSegBatch + 1];
-    const int2 spans = item_span[blockIdx.x];
-    const int64_t c0 = item_k0[blockIdx.x], c1 = item_k1[blockIdx.x];
-    if (spans.y - spans.x == 1) {                        // one segment (always, on the global tile order)
-        const int64_t a0 = seg_off[(int64_t)spans.x * ntiles + b], a1 = seg_off[(int64_t)spans.x * ntiles + b + 1];
-        const int64_t k0 = a0 > c0 ? a0 : c0, k1 = a1 < c1 ? a1 : c1;
-        for (int64_t k = k0 + threadIdx.x; k < k1; k += blockDim.x) {
-            int q;
-            double cc, ss;
-            tile_sample<POL, HALF>(pl, c, s, k, q, cc, ss);
-            double r = 0.0;
-            if (POL == 1) {
-                r += tile[q];
-            } else if (POL == 2) {
-                r += tile[2 * q] * cc + tile[2 * q + 1] * ss;
-            } else {
-                r += tile[3 * q] + tile[3 * q + 1] * cc + tile[3 * q + 2] * ss;
-            }
-            d_tb[k] = r;
+    const int64_t k0 = item_k0[blockIdx.x], k1 = item_k1[blockIdx.x];
+    for (int64_t k = k0 + threadIdx.x; k < k1; k += blockDim.x) {
+        int q;
+        double cc, ss;
+        tile_sample<POL, HALF>(pl, c, s, k, q, cc, ss);
+        double r = 0.0;
+        if (POL == 1) {
+            r += tile[q];
+        } else if (POL == 2) {
+            r += tile[2 * q] * cc + tile[2 * q + 1] * ss;
+        } else {
+            r += tile[3 * q] + tile[3 * q + 1] * cc + tile[3 * q + 2] * ss;
         }
-        return;
-    }
-    for (int sp0 = spans.x; sp0 < spans.y; sp0 += kSegBatch) {
-        const int ns = spans.y - sp0 < kSegBatch ? spans.y - sp0 : kSegBatch;
-        if ((int)threadIdx.x < ns) {
-            const int64_t a0 = seg_off[(int64_t)(sp0 + threadIdx.x) * ntiles + b];
-            const int64_t a1 = seg_off[(int64_t)(sp0 + threadIdx.x) * ntiles + b + 1];
-            const int64_t k0 = a0 > c0 ? a0 : c0, k1 = a1 < c1 ? a1 : c1;
-            seg_k0[threadIdx.x] = k0;
-            seg_pre[threadIdx.x + 1] = (uint32_t)(k1 > k0 ? k1 - k0 : 0);
-        }
-        if (threadIdx.x == 0) seg_pre[0] = 0;
-        __syncthreads();
-        if (threadIdx.x == 0)
-            for (int i = 0; i < ns; ++i) seg_pre[i + 1] += seg_pre[i];
-        __syncthreads();
-        const uint32_t total = seg_pre[ns];
-        int si = 0;
-        for (uint32_t j = threadIdx.x; j < total; j += blockDim.x) {
-            while (j >= seg_pre[si + 1]) ++si;
-            const int64_t k = seg_k0[si] + (int64_t)(j - seg_pre[si]);
-            int q;
-            double cc, ss;
-            tile_sample<POL, HALF>(pl, c, s, k, q, cc, ss);
-            double r = 0.0;
-            if (POL == 1) {
-                r += tile[q];
-            } else if (POL == 2) {
-                r += tile[2 * q] * cc + tile[2 * q + 1] * ss;
-            } else {
-                r += tile[3 * q] + tile[3 * q + 1] * cc + tile[3 * q + 2] * ss;
-            }
-            d_tb[k] = r;
-        }
-        __syncthreads();
+        d_tb[k] = r;
     }
 }
 
 // ---------------------------------------------------------------- P^T (TB) ------
+// (launched with kPtBlock threads.  The strides are compile-time constants: with blockDim.x the
+// compiler kept a 64-bit address per unrolled load in VGPRs, 80 instead of 38 at pol = 3)
 template <int POL, bool HALF>
-__global__ __launch_bounds__(1024) void k_Pt_tiles(
+__global__ __launch_bounds__(kPtBlock) void k_Pt_tiles(
     const int64_t *__restrict__ tile_p0, const int32_t *__restrict__ item_tile,
-    const int2 *__restrict__ item_span, const int64_t *__restrict__ seg_off, int64_t ntiles,
     const int64_t *__restrict__ item_k0, const int64_t *__restrict__ item_k1,
     const uint16_t *__restrict__ pl, const double *__restrict__ c, const double *__restrict__ s,
     const double *__restrict__ v_tb, double *__restrict__ out)
@@ -506,32 +452,17 @@ __global__ __launch_bounds__(1024) void k_Pt_tiles(
     const int64_t p0 = tile_p0[b];
     const int64_t np = tile_p0[b + 1] - p0;
     const int64_t nvals = np * POL;
-    for (int64_t i = threadIdx.x; i < nvals; i += blockDim.x) tile[i] = 0.0;
+    for (int64_t i = threadIdx.x; i < nvals; i += kPtBlock) tile[i] = 0.0;
     __syncthreads();
-    __shared__ int64_t seg_b0[kSegBatch], seg_b1[kSegBatch];
-    const int2 spans = item_span[blockIdx.x];
-    const int64_t clip0 = item_k0[blockIdx.x], clip1 = item_k1[blockIdx.x];
-    for (int sp = spans.x; sp < spans.y; ++sp) {
-    // (the segment bounds of a batch are fetched together, not one dependent load per segment)
-    if ((sp - spans.x) % kSegBatch == 0) {
-        __syncthreads();
-        const int ns = spans.y - sp < kSegBatch ? spans.y - sp : kSegBatch;
-        if ((int)threadIdx.x < ns) {
-            seg_b0[threadIdx.x] = seg_off[(int64_t)(sp + threadIdx.x) * ntiles + b];
-            seg_b1[threadIdx.x] = seg_off[(int64_t)(sp + threadIdx.x) * ntiles + b + 1];
-        }
-        __syncthreads();
-    }
-    const int64_t a0 = seg_b0[(sp - spans.x) % kSegBatch], a1 = seg_b1[(sp - spans.x) % kSegBatch];
-    const int64_t k0 = a0 > clip0 ? a0 : clip0, k1 = a1 < clip1 ? a1 : clip1;
+    const int64_t k1 = item_k1[blockIdx.x];
     constexpr int U = 4;                     // independent loads in flight per thread
-    int64_t k = k0 + threadIdx.x;
-    for (; k + (U - 1) * (int64_t)blockDim.x < k1; k += U * (int64_t)blockDim.x) {
+    int64_t k = item_k0[blockIdx.x] + threadIdx.x;
+    for (; k + (U - 1) * kPtBlock < k1; k += U * kPtBlock) {
         int q[U];
         double v[U], cc[U], ss[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const int64_t kk = k + u * (int64_t)blockDim.x;
+            const int64_t kk = k + u * kPtBlock;
             v[u] = v_tb[kk];
             tile_sample<POL, HALF>(pl, c, s, kk, q[u], cc[u], ss[u]);
         }
@@ -549,7 +480,7 @@ __global__ __launch_bounds__(1024) void k_Pt_tiles(
             }
         }
     }
-    for (; k < k1; k += blockDim.x) {
+    for (; k < k1; k += kPtBlock) {
         int q;
         double c1, s1;
         tile_sample<POL, HALF>(pl, c, s, k, q, c1, s1);
@@ -565,10 +496,9 @@ __global__ __launch_bounds__(1024) void k_Pt_tiles(
             atomicAdd(&tile[3 * q + 2], v * s1);
         }
     }
-    }
     __syncthreads();
     double *o = out + p0 * POL;
-    for (int64_t i = threadIdx.x; i < nvals; i += blockDim.x) atomicAdd(&o[i], tile[i]);
+    for (int64_t i = threadIdx.x; i < nvals; i += kPtBlock) atomicAdd(&o[i], tile[i]);
 }
 
 // ------------------------------------------------------- time <-> TB order ------
@@ -673,20 +603,6 @@ __global__ __launch_bounds__(256) void k_perm_unpack(int64_t total, const uint64
         lst_k[g] = (uint32_t)(keys[g] & 0xFFFFFFFFull);
 }
 
-// workgroup size of the two tile kernels: 1024 threads for the gather (0.355 vs 0.38 ms at
-// 1e8 samples), 512 for the scatter (no difference); CM2_TILE_BLOCK = 256 / 512 / 1024 sets both
-static int tile_block(bool gather = false)
-{
-    static int forced = -1;
-    if (forced < 0) {
-        forced = 0;
-        if (const char *e = getenv("CM2_TILE_BLOCK")) {
-            const int v = atoi(e);
-            if (v == 256 || v == 512 || v == 1024) forced = v;
-        }
-    }
-    return forced ? forced : (gather ? 1024 : 512);
-}
 
 // ------------------------------------------------------------------ C ABI -------
 extern "C" int cm2_tiles_destroy(cm2_tiles *t);
@@ -694,8 +610,8 @@ extern "C" int cm2_tiles_destroy(cm2_tiles *t);
 extern "C" int cm2_tiles_destroy(cm2_tiles *t)
 {
     if (!t) return 0;
-    void *ptrs[] = {t->d_tb_dst, t->d_pl, t->d_cos, t->d_sin, t->d_half, t->d_item_tile, t->d_item_span,
-                    t->d_item_k0, t->d_item_k1, t->d_perm_k, t->d_perm_q, t->d_seg_off, t->d_tile_p0};
+    void *ptrs[] = {t->d_tb_dst, t->d_pl, t->d_cos, t->d_sin, t->d_half, t->d_item_tile, t->d_item_k0,
+                    t->d_item_k1, t->d_perm_k, t->d_perm_q, t->d_tile_off, t->d_tile_p0};
     for (void *q : ptrs)
         if (q) (void)cm2::dev_free(q);
     cm2::fx_free(t);
@@ -703,13 +619,6 @@ extern "C" int cm2_tiles_destroy(cm2_tiles *t)
     return 0;
 }
 
-// The tile order cut in time ([span][tile][time], rounds 4-5) is GONE as an option: measured again in round 5
-// with spans sized for the Infinity Cache (profiles/r05_spans_removed.md: C4 step 1.41 ms on the global order
-// against 1.43 / 1.48 / 1.57 with spans of 9.4e5 / 1.7e7 / 8.4e6 samples; C5 share 1.99 against 2.05-2.06; at
-// C5 whole N^-1 did not move at all) it never paid, and round 4's switch (CM2_TILE_SPAN), its automatic span
-// length and its 71 tests were removed.  What remains of it is the GENERAL form of the tables the kernels walk --
-// segment (span, tile) with ONE span: a tile's segment is its whole bucket, `seg_off` is the tile offsets,
-// every work item is one tile's address range -- which costs nothing and is what the builders were tested on.
 extern "C" int cm2_tiles_create(cm2_tiles **out, const int32_t *d_pix, const double *d_cos,
                                 const double *d_sin, int64_t nt, int64_t npix, int pol,
                                 int tile_pixels, int64_t slice_samples, void *stream_)
@@ -742,7 +651,6 @@ extern "C" int cm2_tiles_create(cm2_tiles **out, const int32_t *d_pix, const dou
     DevTemp<uint32_t> keys_in, keys_out, vals_in, tb_src;      // sort path
     DevTemp<uint32_t> packed, cnt_t;                           // multisplit: tile << 16 | rank; counts -> bases
     const int64_t nchunks = (nt + kSplitChunk - 1) / kSplitChunk;
-    int64_t G = nchunks;                                       // chunks per span (nchunks: one span)
     DevTemp<int64_t> d_off;
     DevTemp<char> d_temp;
     DevTemp<unsigned int> d_bad;
@@ -776,17 +684,16 @@ extern "C" int cm2_tiles_create(cm2_tiles **out, const int32_t *d_pix, const dou
         return 0;
     };
     auto partition_split = [&](const int64_t *d_p0) -> int {
-        const int64_t ncnt = t->nspans * t->ntiles * G + 1;    // (+1: the scan's last word = nvalid)
+        const int64_t ncnt = t->ntiles * nchunks + 1;          // (+1: the scan's last word = nvalid)
         if (!packed.p) CM2_HIP(packed.alloc(nt));
         cnt_t.release();
         CM2_HIP(cnt_t.alloc(ncnt));
-        // (the last span is padded to G chunks: the counts of chunks that do not exist stay 0)
         CM2_HIP(hipMemsetAsync(cnt_t.p, 0, sizeof(uint32_t) * ncnt, stream));
         const size_t lds = sizeof(uint16_t) * 4 * (size_t)t->ntiles;
         static size_t granted[64] = {0};
         CM2_HIP(ensure_dynamic_lds((const void *)k_tile_rank, lds, granted));
         k_tile_rank<<<(unsigned)((nchunks + 3) / 4), 256, lds, stream>>>(
-            d_pix, nt, tile_pixels, d_p0, (uint32_t)t->ntiles, npix, nchunks, G, packed, cnt_t, d_bad);
+            d_pix, nt, tile_pixels, d_p0, (uint32_t)t->ntiles, npix, nchunks, packed, cnt_t, d_bad);
         CM2_LAUNCH_OK();
         CM2_CHECK(ncnt < ((int64_t)1 << 31), "cm2_tiles_create: %lld tile x chunk counts", (long long)ncnt);
         size_t tb = 0;
@@ -794,33 +701,20 @@ extern "C" int cm2_tiles_create(cm2_tiles **out, const int32_t *d_pix, const dou
         d_temp.release();
         CM2_HIP(d_temp.alloc(tb + 16));
         CM2_HIP(hipcub::DeviceScan::ExclusiveSum(d_temp.p, tb, cnt_t.p, cnt_t.p, (int)ncnt, stream));
-        const int64_t nsegs = t->nspans * t->ntiles;
-        k_tile_offsets<<<(int)((nsegs + 1 + kBlock - 1) / kBlock), kBlock, 0, stream>>>(cnt_t, G, nsegs, d_off);
+        k_tile_offsets<<<(int)((t->ntiles + 1 + kBlock - 1) / kBlock), kBlock, 0, stream>>>(cnt_t, nchunks,
+                                                                                            t->ntiles, d_off);
         CM2_LAUNCH_OK();
         return 0;
     };
-    // `seg`: first address of every segment (span, tile); `off`: samples of every tile, as offsets
-    std::vector<int64_t> seg;
+    // `off`: first address of every tile
     auto partition = [&](const int64_t *d_p0) -> int {
         d_off.release();
         sorted = use_sort || t->ntiles > kSplitMaxTiles || t->ntiles * nchunks + 1 >= ((int64_t)1 << 31);
-        G = nchunks;                                        // one span: the global tile order
-        t->nspans = (nchunks + G - 1) / G;
-        if (t->nspans < 1) t->nspans = 1;
-        t->span_samples = G * kSplitChunk;
-        const int64_t nsegs = t->nspans * t->ntiles;
-        CM2_HIP(d_off.alloc(nsegs + 1));
+        CM2_HIP(d_off.alloc(t->ntiles + 1));
         if (int rc = sorted ? partition_sort(d_p0) : partition_split(d_p0)) return rc;
-        seg.assign((size_t)nsegs + 1, 0);
-        CM2_HIP(cm2::download(seg.data(), d_off, sizeof(int64_t) * (nsegs + 1), stream));
-        CM2_HIP(hipStreamSynchronize(stream));
         off.assign((size_t)t->ntiles + 1, 0);
-        for (int64_t b = 0; b < t->ntiles; ++b) {
-            int64_t n = 0;
-            for (int64_t sp = 0; sp < t->nspans; ++sp)
-                n += seg[(size_t)(sp * t->ntiles + b + 1)] - seg[(size_t)(sp * t->ntiles + b)];
-            off[(size_t)b + 1] = off[(size_t)b] + n;
-        }
+        CM2_HIP(cm2::download(off.data(), d_off, sizeof(int64_t) * (t->ntiles + 1), stream));
+        CM2_HIP(hipStreamSynchronize(stream));
         return 0;
     };
     if (int rc = partition(nullptr)) return rc;
@@ -957,17 +851,10 @@ extern "C" int cm2_tiles_create(cm2_tiles **out, const int32_t *d_pix, const dou
     CM2_HIP(cm2::dev_malloc(&t->d_tile_p0, sizeof(int64_t) * (t->ntiles + 1)));
     CM2_HIP(cm2::upload(t->d_tile_p0, t->tile_p0.data(), sizeof(int64_t) * (t->ntiles + 1), nullptr));
     t->nvalid = off[t->ntiles];
-    auto publish_segments = [&]() -> int {
-        t->tile_count.assign((size_t)t->ntiles, 0);
-        for (int64_t b = 0; b < t->ntiles; ++b) t->tile_count[(size_t)b] = off[(size_t)b + 1] - off[(size_t)b];
-        t->seg_off = seg;
-        if (t->d_seg_off) (void)cm2::dev_free(t->d_seg_off);
-        t->d_seg_off = nullptr;
-        CM2_HIP(cm2::dev_malloc(&t->d_seg_off, sizeof(int64_t) * seg.size()));
-        CM2_HIP(hipMemcpyAsync(t->d_seg_off, d_off, sizeof(int64_t) * seg.size(), hipMemcpyDeviceToDevice, stream));
-        return 0;
-    };
-    if (int rc = publish_segments()) return rc;
+    t->tile_count.assign((size_t)t->ntiles, 0);
+    for (int64_t b = 0; b < t->ntiles; ++b) t->tile_count[(size_t)b] = off[(size_t)b + 1] - off[(size_t)b];
+    t->tile_off = off;
+    t->d_tile_off = d_off.keep();
 
     const int64_t nv = t->nvalid > 0 ? t->nvalid : 1;
     CM2_HIP(cm2::dev_malloc(&t->d_tb_dst, sizeof(uint32_t) * nt));
@@ -1012,11 +899,11 @@ extern "C" int cm2_tiles_create(cm2_tiles **out, const int32_t *d_pix, const dou
             static size_t granted[64] = {0};                                                   \
             CM2_HIP(ensure_dynamic_lds((const void *)k_tile_place_staged<POL>, lds, granted));  \
             k_tile_place_staged<POL><<<(unsigned)nchunks, 256, lds, stream>>>(                 \
-                nt, tile_pixels, balance ? t->d_tile_p0 : nullptr, G, (int)t->ntiles,          \
+                nt, tile_pixels, balance ? t->d_tile_p0 : nullptr, (int)t->ntiles,             \
                 packed, cnt_t, d_pix, d_cos, d_sin, t->d_tb_dst, t->d_pl, t->d_half);          \
         } else                                                                                 \
             k_tile_place<POL, HALF><<<grid_for(nt), kBlock, 0, stream>>>(                      \
-                nt, tile_pixels, balance ? t->d_tile_p0 : nullptr, t->ntiles, G, packed, cnt_t, \
+                nt, tile_pixels, balance ? t->d_tile_p0 : nullptr, packed, cnt_t,              \
                 d_pix, d_cos, d_sin, t->d_tb_dst, t->d_pl, HALF ? t->d_half : t->d_cos,        \
                 t->d_sin);                                                                     \
     } while (0)
@@ -1028,53 +915,27 @@ extern "C" int cm2_tiles_create(cm2_tiles **out, const int32_t *d_pix, const dou
     return 0;
     };
     if (int rc = place()) return rc;
-    // work items: a tile's segments in span order, gathered until they hold >= slice_samples samples; a
-    // segment longer than that (one span: the whole bucket) is cut into address ranges
+    // work items: every tile's bucket cut into address ranges of at most slice_samples (none for an empty one)
     std::vector<int32_t> it_tile;
-    std::vector<int2> it_span;
     std::vector<int64_t> it_k0, it_k1;
     t->tile_item0.assign((size_t)t->ntiles + 1, 0);
     for (int64_t b = 0; b < t->ntiles; ++b) {
         t->tile_item0[(size_t)b] = (int64_t)it_tile.size();
-        int64_t sp = 0;
-        while (sp < t->nspans) {
-            const int64_t a0 = seg[(size_t)(sp * t->ntiles + b)], a1 = seg[(size_t)(sp * t->ntiles + b + 1)];
-            if (a1 - a0 > slice_samples) {
-                for (int64_t k = a0; k < a1; k += slice_samples) {
-                    it_tile.push_back((int32_t)b);
-                    it_span.push_back(make_int2((int)sp, (int)sp + 1));
-                    it_k0.push_back(k);
-                    it_k1.push_back(k + slice_samples < a1 ? k + slice_samples : a1);
-                }
-                ++sp;
-                continue;
-            }
-            int64_t n = 0, e = sp;
-            while (e < t->nspans) {
-                const int64_t len = seg[(size_t)(e * t->ntiles + b + 1)] - seg[(size_t)(e * t->ntiles + b)];
-                if (len > slice_samples || (n > 0 && n + len > slice_samples)) break;
-                n += len;
-                ++e;
-            }
-            if (n > 0) {
-                it_tile.push_back((int32_t)b);
-                it_span.push_back(make_int2((int)sp, (int)e));
-                it_k0.push_back(0);
-                it_k1.push_back(INT64_MAX);
-            }
-            sp = e;
+        const int64_t a1 = off[(size_t)b + 1];
+        for (int64_t k = off[(size_t)b]; k < a1; k += slice_samples) {
+            it_tile.push_back((int32_t)b);
+            it_k0.push_back(k);
+            it_k1.push_back(k + slice_samples < a1 ? k + slice_samples : a1);
         }
     }
     t->tile_item0[(size_t)t->ntiles] = (int64_t)it_tile.size();
     t->nitems = (int64_t)it_tile.size();
     const int64_t ni = t->nitems > 0 ? t->nitems : 1;
     CM2_HIP(cm2::dev_malloc(&t->d_item_tile, sizeof(int32_t) * ni));
-    CM2_HIP(cm2::dev_malloc(&t->d_item_span, sizeof(int2) * ni));
     CM2_HIP(cm2::dev_malloc(&t->d_item_k0, sizeof(int64_t) * ni));
     CM2_HIP(cm2::dev_malloc(&t->d_item_k1, sizeof(int64_t) * ni));
     if (t->nitems) {
         CM2_HIP(cm2::upload(t->d_item_tile, it_tile.data(), sizeof(int32_t) * ni, nullptr));
-        CM2_HIP(cm2::upload(t->d_item_span, it_span.data(), sizeof(int2) * ni, nullptr));
         CM2_HIP(cm2::upload(t->d_item_k0, it_k0.data(), sizeof(int64_t) * ni, nullptr));
         CM2_HIP(cm2::upload(t->d_item_k1, it_k1.data(), sizeof(int64_t) * ni, nullptr));
     }
@@ -1091,7 +952,8 @@ extern "C" int cm2_tiles_info(const cm2_tiles *t, int64_t *h_info)
     h_info[3] = t->ntiles; h_info[4] = t->nitems; h_info[5] = t->half ? 1 : 0;
     h_info[6] = t->pt_fixed; h_info[7] = (int64_t)t->plan_id;
     h_info[8] = t->fx_S; h_info[9] = cm2::fx_designed_bytes(t);
-    h_info[10] = t->nspans; h_info[11] = t->span_samples;
+    // (the two fields of the span order removed in round 5: one span of all the chunks of kSplitChunk samples)
+    h_info[10] = 1; h_info[11] = (t->nt + kSplitChunk - 1) / kSplitChunk * kSplitChunk;
     return 0;
 }
 
@@ -1118,11 +980,8 @@ extern "C" int cm2_tiles_set_pt_order(cm2_tiles *t, int fixed)
 extern "C" uint64_t cm2_tiles_plan_id(const cm2_tiles *t) { return t ? t->plan_id : 0; }
 extern "C" int64_t cm2_tiles_ntiles(const cm2_tiles *t) { return t ? t->ntiles : 0; }
 extern "C" int64_t cm2_tiles_nvalid(const cm2_tiles *t) { return t ? t->nvalid : 0; }
-// first tile-order address of every segment (span, tile), [nspans * ntiles + 1] on the device, and the
-// samples per span (internal: cm2_noise.hip)
-extern "C" const int64_t *cm2_tiles_offsets(const cm2_tiles *t) { return t ? t->d_seg_off : nullptr; }
-extern "C" int64_t cm2_tiles_nspans(const cm2_tiles *t) { return t ? t->nspans : 1; }
-extern "C" int64_t cm2_tiles_span_samples(const cm2_tiles *t) { return t ? t->span_samples : 0; }
+// first tile-order address of every tile, [ntiles + 1] on the device (internal: cm2_noise.hip)
+extern "C" const int64_t *cm2_tiles_offsets(const cm2_tiles *t) { return t ? t->d_tile_off : nullptr; }
 
 // Tile indices bounding `ngroups` consecutive groups of tiles whose PIXEL boundaries are the same on
 // every rank of a sharded run (ranks with different hit maps may have cut their tiles differently):
@@ -1174,9 +1033,9 @@ extern "C" int cm2_P_tiles_apply(const cm2_tiles *t, const double *d_x, double *
     hipStream_t stream = as_stream(stream_);
     const size_t lds = sizeof(double) * t->tp * t->pol;
 #define CM2_PT(POL, HALF)                                                                      \
-    k_P_tiles<POL, HALF><<<(int)t->nitems, tile_block(true), lds, stream>>>(                       \
-        t->d_tile_p0, t->d_item_tile, t->d_item_span, t->d_seg_off, t->ntiles, t->d_item_k0,   \
-        t->d_item_k1, t->d_pl, HALF ? t->d_half : t->d_cos, t->d_sin, d_x, d_tod_tb)
+    k_P_tiles<POL, HALF><<<(int)t->nitems, kPBlock, lds, stream>>>(                            \
+        t->d_tile_p0, t->d_item_tile, t->d_item_k0, t->d_item_k1, t->d_pl,                     \
+        HALF ? t->d_half : t->d_cos, t->d_sin, d_x, d_tod_tb)
     if (t->pol == 1) CM2_PT(1, false);
     else if (t->pol == 2) { if (t->half) CM2_PT(2, true); else CM2_PT(2, false); }
     else { if (t->half) CM2_PT(3, true); else CM2_PT(3, false); }
@@ -1197,9 +1056,9 @@ extern "C" int cm2_Pt_tiles_apply(const cm2_tiles *t, const double *d_tod_tb, do
     if (t->nitems == 0) return 0;
     const size_t lds = sizeof(double) * t->tp * t->pol;
 #define CM2_PTT(POL, HALF)                                                                     \
-    k_Pt_tiles<POL, HALF><<<(int)t->nitems, tile_block(), lds, stream>>>(                      \
-        t->d_tile_p0, t->d_item_tile, t->d_item_span, t->d_seg_off, t->ntiles, t->d_item_k0,   \
-        t->d_item_k1, t->d_pl, HALF ? t->d_half : t->d_cos, t->d_sin, d_tod_tb, d_out)
+    k_Pt_tiles<POL, HALF><<<(int)t->nitems, kPtBlock, lds, stream>>>(                          \
+        t->d_tile_p0, t->d_item_tile, t->d_item_k0, t->d_item_k1, t->d_pl,                     \
+        HALF ? t->d_half : t->d_cos, t->d_sin, d_tod_tb, d_out)
     if (t->pol == 1) CM2_PTT(1, false);
     else if (t->pol == 2) { if (t->half) CM2_PTT(2, true); else CM2_PTT(2, false); }
     else { if (t->half) CM2_PTT(3, true); else CM2_PTT(3, false); }
@@ -1226,10 +1085,9 @@ extern "C" int cm2_Pt_tiles_apply_range(const cm2_tiles *t, const double *d_tod_
     if (i1 == i0) return 0;
     const size_t lds = sizeof(double) * t->tp * t->pol;
 #define CM2_PTR(POL, HALF)                                                                     \
-    k_Pt_tiles<POL, HALF><<<(int)(i1 - i0), tile_block(), lds, stream>>>(                      \
-        t->d_tile_p0, t->d_item_tile + i0, t->d_item_span + i0, t->d_seg_off, t->ntiles,      \
-        t->d_item_k0 + i0, t->d_item_k1 + i0, t->d_pl, HALF ? t->d_half : t->d_cos, t->d_sin,  \
-        d_tod_tb, d_out)
+    k_Pt_tiles<POL, HALF><<<(int)(i1 - i0), kPtBlock, lds, stream>>>(                          \
+        t->d_tile_p0, t->d_item_tile + i0, t->d_item_k0 + i0, t->d_item_k1 + i0, t->d_pl,      \
+        HALF ? t->d_half : t->d_cos, t->d_sin, d_tod_tb, d_out)
     if (t->pol == 1) CM2_PTR(1, false);
     else if (t->pol == 2) { if (t->half) CM2_PTR(2, true); else CM2_PTR(2, false); }
     else { if (t->half) CM2_PTR(3, true); else CM2_PTR(3, false); }
@@ -1271,17 +1129,12 @@ static inline void perm_geometry(int64_t nt, int &blocks, int64_t &chunk)
     if (blocks < 1) blocks = 1;
 }
 
-// lists of the windowed permutations (CM2_PERM_WINDOWS=0 keeps the per-sample kernels)
+// lists of the windowed permutations (a TOD shorter than one window keeps the per-sample kernels)
 static int perm_lists(const cm2_tiles *tc, hipStream_t st, bool *use)
 {
     cm2_tiles *t = const_cast<cm2_tiles *>(tc);         // lazily built cache
-    static int enabled = -1;
-    if (enabled < 0) {
-        const char *e = getenv("CM2_PERM_WINDOWS");
-        enabled = e ? atoi(e) : 1;
-    }
     *use = false;
-    if (!enabled || t->nt < kPermWin) return 0;
+    if (t->nt < kPermWin) return 0;
     if (!t->d_perm_k) {
         const int64_t nwin = (t->nt + kPermWin - 1) / kPermWin, total = nwin * kPermWin;
         DevTemp<uint64_t> keys_in, keys_out;

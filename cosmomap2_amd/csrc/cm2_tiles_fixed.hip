@@ -279,8 +279,7 @@ __global__ __launch_bounds__(kFxT, 4) void k_Pt_tiles_fixed(
     uint2 pm[D][2];                                      // meta of slice j and j + 1
     // {first group, first tail run} of the NEXT slice to fetch and of its successor: loaded one
     // fetch ahead, so that the group addresses never wait for them
-    // ... and {first TB address, samples} of it: the slices of a tile are its segments (one per span
-    // of the plan, cut where longer than the slice length), not consecutive addresses
+    // ... and {first TB address, samples} of it
     uint2 nx0 = meta[s0], nx1 = meta[s0 + (nsl > 0 ? 1 : 0)], nk = sk[s0];
     auto fetch = [&](int slot, int j) {
         const int64_t kb = (int64_t)nk.x;
@@ -1026,13 +1025,11 @@ int hot_plan(cm2_tiles *t, hipStream_t st)
         if (t->tile_p0[(size_t)b + 1] - t->tile_p0[(size_t)b] != 1 || n < kHotMin) continue;
         flag[(size_t)b] = 1;
         const int64_t c0 = (int64_t)range.size() / 2;
-        // (ranges in time order: span after span, kHotChunk consecutive samples of a segment each)
-        for (int64_t sp = 0; sp < t->nspans; ++sp) {
-            const int64_t a0 = t->seg_off[(size_t)(sp * t->ntiles + b)], a1 = t->seg_off[(size_t)(sp * t->ntiles + b + 1)];
-            for (int64_t k = a0; k < a1; k += kHotChunk) {
-                range.push_back(k);
-                range.push_back(k + kHotChunk < a1 ? k + kHotChunk : a1);
-            }
+        // (ranges in time order: kHotChunk consecutive samples of the bucket each)
+        const int64_t a1 = t->tile_off[(size_t)b + 1];
+        for (int64_t k = t->tile_off[(size_t)b]; k < a1; k += kHotChunk) {
+            range.push_back(k);
+            range.push_back(k + kHotChunk < a1 ? k + kHotChunk : a1);
         }
         tiles.push_back(t->tile_p0[(size_t)b]);
         tiles.push_back(c0);
@@ -1100,30 +1097,18 @@ static bool fx_hot_tile(const cm2_tiles *t, int64_t b)
 }
 
 // The slices of the plan for the slice length S, as (first address, end) pairs in the order the
-// kernel walks them: tile after tile, a tile's segments span after span (= in time), a segment cut
-// where it is longer than S -- into pieces of S with a shorter last one when the plan has one span
-// (the tile's whole bucket is one segment: rounds 1-3), into equal pieces otherwise (a segment is
-// about one slice long by the choice of the span: cutting 2100 samples into 1856 + 244 would cost a
-// whole barrier round for the short piece).  slice0[b] = first slice of tile b.
+// kernel walks them: tile after tile, a tile's bucket cut into pieces of S with a shorter last one.
+// slice0[b] = first slice of tile b.
 static void fx_slices(const cm2_tiles *t, int S, std::vector<int64_t> &slice0, std::vector<int64_t> &pairs)
 {
     slice0.assign((size_t)t->ntiles + 1, 0);
     pairs.clear();
     for (int64_t b = 0; b < t->ntiles; ++b) {
         slice0[(size_t)b] = (int64_t)pairs.size() / 2;
-        for (int64_t sp = 0; sp < t->nspans; ++sp) {
-            const int64_t a0 = t->seg_off[(size_t)(sp * t->ntiles + b)], a1 = t->seg_off[(size_t)(sp * t->ntiles + b + 1)];
-            if (a1 <= a0) continue;
-            int64_t piece = S;
-            if (t->nspans > 1) {
-                const int64_t np = (a1 - a0 + S - 1) / S;
-                piece = ((a1 - a0 + np - 1) / np + 63) / 64 * 64;
-                if (piece > S) piece = S;
-            }
-            for (int64_t k = a0; k < a1; k += piece) {
-                pairs.push_back(k);
-                pairs.push_back(k + piece < a1 ? k + piece : a1);
-            }
+        const int64_t a1 = t->tile_off[(size_t)b + 1];
+        for (int64_t k = t->tile_off[(size_t)b]; k < a1; k += S) {
+            pairs.push_back(k);
+            pairs.push_back(k + S < a1 ? k + S : a1);
         }
     }
     slice0[(size_t)t->ntiles] = (int64_t)pairs.size() / 2;
@@ -1145,12 +1130,11 @@ int fx_estimate(const cm2_tiles *t, int S, hipStream_t st, double *mean_groups, 
     std::vector<int64_t> pairs, slice0, all;
     fx_slices(t, S, slice0, all);
     int64_t seen = 0;
-    // (one span: the full slices of S samples; several spans: a slice is a segment, all of them count)
     for (int64_t b = 0; b < t->ntiles; ++b) {
         if (fx_hot_tile(t, b)) continue;
         for (int64_t sl = slice0[(size_t)b]; sl < slice0[(size_t)b + 1]; ++sl) {
             const int64_t k = all[(size_t)(2 * sl)], e = all[(size_t)(2 * sl + 1)];
-            if (t->nspans == 1 && e - k != S) continue;
+            if (e - k != S) continue;                    // (full slices only)
             if (seen++ % 8 == 0) {
                 pairs.push_back(k);
                 pairs.push_back(e);
@@ -1242,8 +1226,7 @@ int fx_build(cm2_tiles *t, int S, hipStream_t st, double *mean_groups, double *o
             CM2_HIP(keys_in.alloc(nv));
             CM2_HIP(keys_out.alloc(nv));
             CM2_HIP(vals_in.alloc(nv));
-            CM2_CHECK(t->nspans == 1, "cm2_tiles: the serial list builders need the global tile order");
-            k_fx_keys<<<grid_for(nv), kBlock, 0, st>>>(nv, t->ntiles, S, qmask, t->d_seg_off,
+            k_fx_keys<<<grid_for(nv), kBlock, 0, st>>>(nv, t->ntiles, S, qmask, t->d_tile_off,
                                                       t->d_fx_slice0, t->d_pl, keys_in, vals_in);
             CM2_LAUNCH_OK();
             int end_bit = 17;
@@ -1283,7 +1266,7 @@ int fx_build(cm2_tiles *t, int S, hipStream_t st, double *mean_groups, double *o
             for (int64_t s = slice0[(size_t)b]; s < slice0[(size_t)b + 1]; ++s) {
                 ++ncounted;
                 if (counts[(size_t)(4 * s)] > (uint32_t)kFxT) ++nover;
-                if (t->nspans > 1 || k0[(size_t)(2 * s + 1)] - k0[(size_t)(2 * s)] == S) {
+                if (k0[(size_t)(2 * s + 1)] - k0[(size_t)(2 * s)] == S) {
                     ++nfull;
                     gsum += counts[(size_t)(4 * s)];
                 }
@@ -1674,10 +1657,6 @@ static int fx_plan_build(const cm2_tiles *tc, hipStream_t st, bool *use)
         double mean = 0.0, over = 0.0;
         if (forced >= 64 && forced <= 4 * kFxT) {
             if (int rc = fx_build(t, forced < smax ? forced : smax, st, &mean, &over)) return rc;
-        } else if (t->nspans > 1) {
-            // the slices are the segments of the plan's spans (the span length was chosen for segments
-            // of ~0.9 smax samples): nothing to tune, S only caps the rare longer segment
-            if (int rc = fx_build(t, smax, st, &mean, &over)) return rc;
         } else {
             int S = 1536 < smax ? 1536 : smax;
             auto wanted = [&](int S_now) {

@@ -200,7 +200,6 @@ class _TileHandle(object):
         self.pt_fixed = bool(info[6])
         self.pt_mode = int(info[6])              # 0 atomic, 1 fixed (hot runs chunked), 2 exact
         self.plan_id = int(info[7])
-        self.nspans, self.span_samples = int(info[10]), int(info[11])
 
     def _info(self):
         info = (ctypes.c_int64 * 12)()

@@ -134,8 +134,7 @@ int cm2_PtNP_diag_apply(const cm2_pointing *p, const double *d_x, double *d_out,
  *   Samples grouped by pixel tile (stable, so time order inside a tile); the tile's
  *   slice of the map is staged in LDS, so P and P^T stream HBM with no random access.
  *   The order is internal: TB-ordered TODs are only ever produced and consumed by the entry points of
- *   this section and cm2_noise_apply_tiles / cm2_filter_apply_tiles.  (Round 4's option to cut the
- *   order in time as well, CM2_TILE_SPAN, never paid and was removed in round 5.)
+ *   this section and cm2_noise_apply_tiles / cm2_filter_apply_tiles.
  *   Same loops as above (linearoperators.py:483-489, :509-516).  P^T by default adds every
  *   pixel's terms in time order from 0 like the serial loop (one workgroup per tile, per-slice
  *   lists sorted by (pixel, time), no atomics: bitwise reproducible); cm2_tiles_set_pt_order(t, 0)

@@ -1,6 +1,6 @@
 # environment-selected variants of the plan against the default, alternated on one box (timed loop of bench.py)
 # usage: bash r04_env_ab.sh "name:VAR=value ..."   (default is always included)
-VARIANTS=${1:-"span_auto:CM2_TILE_SPAN=auto lists_inv:CM2_OS_LISTS=inv"}
+VARIANTS=${1:-"lists_inv:CM2_OS_LISTS=inv"}
 for rep in 1 2 3 4 5; do
 for v in default $VARIANTS; do
   name=${v%%:*}

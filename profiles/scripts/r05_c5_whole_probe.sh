@@ -2,8 +2,7 @@
 # Why does N^-1 cost 43 % more per sample at C5 WHOLE (1e9 samples, TOD buffers of 8 GB) than on one GPU's share
 # (1.25e8, 1 GB)?    Same nside, tiles, lists and run lengths; what differs is the
 # address range a window's ~1500 runs are spread over.
-#   part 1: timed loop of bench.py at both sizes, global tile order against the span order (CM2_TILE_SPAN: a
-#           window's addresses then live inside one span), alternated
+#   part 1: timed loop of bench.py at both sizes, alternated
 #   part 2: counters of k_os_real at both sizes, <= 2 counters of one block per pass (prof_os_counters.sh says why)
 # Usage: bash profiles/scripts/r05_c5_whole_probe.sh [timing|counters|both]
 set -o pipefail
@@ -28,9 +27,6 @@ if [ "$what" != counters ]; then
   for rep in 1 2; do
     line share_default_$rep "" CM2_X=0 || exit 1
     line whole_default_$rep "--scaling strong --gpus 1" CM2_X=0 || exit 1
-    line whole_span_auto_$rep "--scaling strong --gpus 1" CM2_TILE_SPAN=auto || exit 1
-    line whole_span_8M_$rep "--scaling strong --gpus 1" CM2_TILE_SPAN=8388608 || exit 1
-    line whole_span_64M_$rep "--scaling strong --gpus 1" CM2_TILE_SPAN=67108864 || exit 1
   done
 fi
 if [ "$what" != timing ]; then
