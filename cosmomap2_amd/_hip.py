@@ -103,6 +103,11 @@ PROTOTYPES = {
     "cm2_fullsky_to_cutsky": [_int, _i64, _vp, _vp, _i64, _vp, _vp],
     "cm2_ground_bin_sums": [_i64, _int, _vp, _vp, _vp, _vp],
     "cm2_ground_subtract": [_i64, _vp, _vp, _vp, _vp, _vp],
+    "cm2_psd_create": [ctypes.POINTER(_vp), _i64, _int, _i64, _vp],
+    "cm2_psd_destroy": [_vp],
+    "cm2_psd_info": [_vp, ctypes.POINTER(_i64)],
+    "cm2_psd_welch": [_vp, _vp, ctypes.POINTER(_i64), _i64, _dbl, _vp, _vp],
+    "cm2_noise_bands_from_psd": [_vp, _i64, _i64, _dbl, _i64, _vp, _vp],
 }
 _RESTYPE = {"cm2_last_error": ctypes.c_char_p, "cm2_reduce_work_doubles": _i64,
             "cm2_gemm_tn_work_doubles": _i64}
@@ -111,7 +116,8 @@ _lib = None
 
 
 class HipError(RuntimeError):
-    pass
+    """A failed library call; ``status`` is its CM2_ERR_* code (None when no library call failed)."""
+    status = None
 
 
 def load():
@@ -134,7 +140,9 @@ def load():
 def check(rc):
     if rc != 0:
         msg = load().cm2_last_error()
-        raise HipError(msg.decode() if msg else "libcosmomap2_hip call failed (rc=%d)" % rc)
+        err = HipError(msg.decode() if msg else "libcosmomap2_hip call failed (rc=%d)" % rc)
+        err.status = rc
+        raise err
 
 
 def _free_torch_cache():
@@ -150,6 +158,7 @@ def _free_torch_cache():
         return False
 
 
+ERR_ARGUMENT = 2               # CM2_ERR_ARGUMENT of include/cosmomap2.h
 ERR_OUT_OF_MEMORY = 3          # CM2_ERR_OUT_OF_MEMORY of include/cosmomap2.h
 
 # Entry points that may be called again after an out-of-memory failure: they build a new object (a failed
@@ -170,6 +179,7 @@ RESTARTABLE = frozenset([
     "cm2_transpose", "cm2_cos_sin_2phi", "cm2_m2_finish",
     "cm2_filter_create", "cm2_filter_apply", "cm2_filter_apply_tiles",
     "cm2_cutsky_to_fullsky", "cm2_fullsky_to_cutsky", "cm2_ground_bin_sums", "cm2_ground_subtract",
+    "cm2_psd_create", "cm2_psd_welch", "cm2_noise_bands_from_psd",
 ])
 
 

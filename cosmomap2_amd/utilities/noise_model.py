@@ -1,0 +1,234 @@
+"""
+Inverse-noise bands estimated from the time streams (the reference has no estimator: its
+``BlockLO`` / ``ToeplitzLO``, interfaces/linearoperators.py:560-697, only define what a band is,
+``y_k = a0 v_k + sum_{i>=1} a_i (v_{k+i} + v_{k-i})``).
+
+    f, psd = noise_psd(d, blocksize, nperseg)          # Welch PSD per noise block, on the GPU
+    bands  = inverse_noise_bands(psd, lam)             # [nb, lam] SPD bands
+    N      = estimate_inverse_noise(d, blocksize, lam) # BlockLO(blocksize, bands, offdiag=True)
+
+``blocksize`` follows ``BlockLO``: an int (equal blocks; ``len(d)`` must be a multiple of it) or a
+list of per-block sizes adding up to ``len(d)``.  ``d`` may be a NumPy array or a float64 tensor in
+HBM; for a tensor nothing of TOD size crosses PCIe and the outputs are device tensors, otherwise
+they are NumPy arrays.  Every argument is checked before the GPU is touched (``ValueError``);
+without a GPU a valid call raises ``HipError`` like every operator constructor.
+
+Estimate from the noise alone: on a bright sky, take a residual such as ``d - P (M_BD P^T d)``
+(the binned sky map scanned back) rather than ``d`` itself, or the sky's power ends up in the
+noise model.  On several GPUs, each rank estimates the whole blocks ``sharding.shard_blocks`` gave
+it, from its own part of the TOD: blocks are independent, no collective is needed.
+"""
+import ctypes
+
+import numpy as np
+
+from .. import _hip
+from .. import device as D
+
+__all__ = ["noise_psd", "inverse_noise_bands", "estimate_inverse_noise"]
+
+_MIN_L, _MAX_L = 256, 65536
+
+
+def _is_pow2(n):
+    return n > 0 and (n & (n - 1)) == 0
+
+
+def _int(name, v):
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+        raise ValueError("%s must be an integer, got %r" % (name, v))
+    return int(v)
+
+
+def _check_fsample(fsample):
+    try:
+        fs = float(fsample)
+    except (TypeError, ValueError):
+        raise ValueError("fsample must be a positive number, got %r" % (fsample,))
+    if not (np.isfinite(fs) and fs > 0):
+        raise ValueError("fsample must be a positive number, got %r" % (fsample,))
+    return fs
+
+
+def _check_nperseg(nperseg):
+    L = _int("nperseg", nperseg)
+    if not (_is_pow2(L) and _MIN_L <= L <= _MAX_L):
+        raise ValueError("nperseg=%d must be a power of two in [%d, %d]" % (L, _MIN_L, _MAX_L))
+    return L
+
+
+def _check_lam(lam, L):
+    lam = _int("lam", lam)
+    if not 1 <= lam <= L // 2:
+        raise ValueError("lam=%d outside [1, nperseg/2 = %d]" % (lam, L // 2))
+    return lam
+
+
+def _tod_length(d):
+    """Number of samples of a 1-D TOD (NumPy array or float64 tensor), without touching the GPU."""
+    if D.is_tensor(d):
+        if D.torch is None or d.dtype != D.torch.float64:
+            raise ValueError("a TOD tensor must be float64, got %s" % d.dtype)
+        if d.dim() != 1:
+            raise ValueError("the TOD must be one-dimensional, got shape %s" % (tuple(d.shape),))
+        return int(d.numel())
+    a = np.asarray(d)
+    if a.ndim != 1:
+        raise ValueError("the TOD must be one-dimensional, got shape %s" % (a.shape,))
+    if not (np.issubdtype(a.dtype, np.floating) or np.issubdtype(a.dtype, np.integer)):
+        raise ValueError("the TOD must be real numbers, got dtype %s" % a.dtype)
+    return int(a.size)
+
+
+def _block_sizes(blocksize, nt):
+    """Per-block sizes of ``blocksize`` (BlockLO's convention) for a TOD of ``nt`` samples."""
+    if np.ndim(blocksize) == 0:
+        bs = _int("blocksize", blocksize)
+        if bs <= 0 or nt % bs:
+            raise ValueError("blocksize=%d does not divide the %d samples of the TOD" % (bs, nt))
+        return [bs] * (nt // bs)
+    sizes = [_int("blocksize[%d]" % i, b) for i, b in enumerate(blocksize)]
+    if not sizes or any(s <= 0 for s in sizes):
+        raise ValueError("blocksize must list positive block sizes, got %r" % (list(blocksize),))
+    if sum(sizes) != nt:
+        raise ValueError("blocksize adds up to %d samples, the TOD has %d" % (sum(sizes), nt))
+    return sizes
+
+
+def _check_detrend(detrend):
+    if detrend is False:
+        return 0
+    if isinstance(detrend, str) and detrend == "constant":
+        return 1
+    raise ValueError("detrend must be 'constant' or False, got %r" % (detrend,))
+
+
+def _check_psd(psd):
+    """(nb, L) of a PSD array [nb, L/2+1] (NumPy array or float64 tensor)."""
+    if D.is_tensor(psd):
+        if psd.dtype != D.torch.float64:
+            raise ValueError("a PSD tensor must be float64, got %s" % psd.dtype)
+        shape = tuple(psd.shape)
+    else:
+        shape = np.shape(psd)
+    if len(shape) != 2 or shape[0] < 1:
+        raise ValueError("the PSD must be an array [nblocks, nperseg/2 + 1], got shape %s" % (shape,))
+    L = 2 * (shape[1] - 1)
+    if not (_is_pow2(L) and _MIN_L <= L <= _MAX_L):
+        raise ValueError("the PSD has %d bins per block: not nperseg/2 + 1 for a power of two nperseg in "
+                         "[%d, %d]" % (shape[1], _MIN_L, _MAX_L))
+    return shape[0], L
+
+
+class _Psd(object):
+    """Owns a cm2_psd handle (plan and workspace of one nperseg)."""
+
+    def __init__(self, L, detrend, work_bytes):
+        self.h = ctypes.c_void_p()
+        _hip.call("cm2_psd_create", ctypes.byref(self.h), int(L), int(detrend), int(work_bytes or 0), D.stream())
+
+    def info(self):
+        info = (ctypes.c_int64 * 3)()
+        _hip.call("cm2_psd_info", self.h, info)
+        return dict(nperseg=int(info[0]), segments_per_batch=int(info[1]), work_bytes=int(info[2]))
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            try:
+                _hip.load().cm2_psd_destroy(self.h)
+            except Exception:
+                pass
+            self.h = None
+
+
+def noise_psd(d, blocksize, nperseg, fsample=1.0, detrend="constant", work_bytes=None):
+    """
+    Welch PSD of every noise block of the TOD ``d``: ``(f, psd)`` with ``f = numpy.fft.rfftfreq(L, 1/fs)``
+    and ``psd[b]`` equal to ``scipy.signal.welch(d_b, fs, window='hann', nperseg=L, noverlap=L//2,
+    detrend=detrend, scaling='density', average='mean')[1]`` of block ``b`` (to rounding).
+
+    ``nperseg`` (L) is a power of two in [256, 65536], no longer than the shortest block; block b
+    has ``(n_b - L) // (L/2) + 1`` segments and a tail that does not fill one is ignored.  ``detrend``
+    is ``'constant'`` (subtract each segment's mean) or ``False``.  The work runs over batches of
+    segments whose buffers take at most ``work_bytes`` (default 512 MB) of device memory; the
+    result of a block does not depend on the other blocks nor on the batch boundaries (summed in
+    segment order).  Estimate from a residual such as ``d - P (M_BD P^T d)`` when the sky is bright.
+    """
+    nt = _tod_length(d)
+    sizes = _block_sizes(blocksize, nt)
+    L = _check_nperseg(nperseg)
+    if L > min(sizes):
+        raise ValueError("nperseg=%d is longer than the shortest block (%d samples)" % (L, min(sizes)))
+    fs = _check_fsample(fsample)
+    dt = _check_detrend(detrend)
+    if work_bytes is not None and _int("work_bytes", work_bytes) <= 0:
+        raise ValueError("work_bytes must be positive, got %r" % (work_bytes,))
+    D.require_gpu()
+    x = D.f64(d)
+    nb = len(sizes)
+    psd = D.empty(nb * (L // 2 + 1))
+    h = _Psd(L, dt, work_bytes)
+    sz = np.ascontiguousarray(sizes, dtype=np.int64)
+    _hip.call("cm2_psd_welch", h.h, D.ptr(x), sz.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), nb, fs,
+              D.ptr(psd), D.stream())
+    del h
+    f = np.fft.rfftfreq(L, 1.0 / fs)
+    psd = psd.view(nb, L // 2 + 1)
+    if D.is_dev(d):
+        return D.f64(f), psd
+    return f, D.to_host(psd)
+
+
+def inverse_noise_bands(psd, lam, fsample=1.0):
+    """
+    First rows ``[nb, lam]`` of SPD banded-Toeplitz inverse-noise blocks from a one-sided PSD
+    ``[nb, L/2+1]`` (from :func:`noise_psd`, or a model evaluated at ``numpy.fft.rfftfreq(L, 1/fs)``):
+
+        S_k = P_k fs / m_k  (m_k = 1 at k = 0 and L/2, else 2),  S_0 := S_1 (the DC bin is not used)
+        G_k = 1 / S_k,   c_j = numpy.fft.irfft(G, L)[j],   a_j = (1 - j/lam) c_j,   1 <= lam <= L/2.
+
+    The Bartlett taper makes the band's symbol G smoothed by the Fejer kernel, which is >= 0: every
+    block built from ``a`` is SPD, with no positivity lift.  White noise of variance s^2 gives
+    ``a ~ (1/s^2, 0, ...)``; ``lam = 1`` gives one white-noise weight per block.  A bin with S <= 0
+    or not finite raises ``ValueError`` naming the block and the bin.
+    """
+    nb, L = _check_psd(psd)
+    lam = _check_lam(lam, L)
+    fs = _check_fsample(fsample)
+    D.require_gpu()
+    p = D.f64(psd)
+    bands = D.empty(nb * lam)
+    try:
+        _hip.call("cm2_noise_bands_from_psd", D.ptr(p), nb, L, fs, lam, D.ptr(bands), D.stream())
+    except _hip.HipError as e:
+        if e.status == _hip.ERR_ARGUMENT:          # the arguments were checked above: a bad bin
+            raise ValueError(str(e)) from None
+        raise
+    bands = bands.view(nb, lam)
+    return bands if D.is_dev(psd) else D.to_host(bands)
+
+
+def estimate_inverse_noise(d, blocksize, lam, nperseg=None, fsample=1.0, detrend="constant", work_bytes=None):
+    """
+    ``BlockLO(blocksize, bands, offdiag=True)`` with the bands estimated from the TOD ``d``:
+    :func:`noise_psd` with ``nperseg`` (default ``max(256, 4 * next_pow2(lam))``), then
+    :func:`inverse_noise_bands`.  Estimate from a residual such as ``d - P (M_BD P^T d)`` when the sky
+    is bright; on several GPUs each rank passes its own blocks (``sharding.shard_blocks``).
+    """
+    lam = _int("lam", lam)
+    if lam < 1:
+        raise ValueError("lam=%d < 1" % lam)
+    if nperseg is None:
+        nperseg = max(_MIN_L, 4 * (1 << (lam - 1).bit_length()))
+    L = _check_nperseg(nperseg)
+    _check_lam(lam, L)
+    nt = _tod_length(d)
+    sizes = _block_sizes(blocksize, nt)
+    if L > min(sizes):
+        raise ValueError("nperseg=%d is longer than the shortest block (%d samples)" % (L, min(sizes)))
+    _check_fsample(fsample)
+    _check_detrend(detrend)
+    _, psd = noise_psd(d, blocksize, L, fsample, detrend, work_bytes)
+    bands = D.to_host(inverse_noise_bands(psd, lam, fsample))
+    from ..interfaces.linearoperators import BlockLO
+    return BlockLO(blocksize, [b for b in bands], offdiag=True)

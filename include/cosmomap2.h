@@ -515,6 +515,35 @@ int cm2_cutsky_to_fullsky(int pol, int64_t npix, const int64_t *d_obspix, const 
 int cm2_fullsky_to_cutsky(int pol, int64_t npix, const int64_t *d_obspix, const double *d_full,
                           int64_t nfull, double *d_map, void *stream);
 
+/* ---- n1: inverse-noise bands estimated from the time streams ---------------------
+ * The reference has no estimator; its ToeplitzLO (linearoperators.py:582-595) defines what a band
+ * means.  L = nperseg is a power of two in [256, 65536].
+ *
+ * cm2_psd_welch: Welch PSD of each block of the TOD d_tod (blocks of h_sizes[0..nb-1] samples, one
+ * after the other, each >= L), d_psd[b][k] for k = 0..L/2 -- scipy.signal.welch(x_b, fs, window='hann',
+ * nperseg=L, noverlap=L/2, detrend='constant' (detrend = 1) or False (0), scaling='density',
+ * average='mean'); block b has K_b = (n_b - L) / (L/2) + 1 segments, a tail that does not fill one is
+ * ignored, and the per-bin sum of |X_s(k)|^2 runs in segment order.  Sample offsets are 64-bit.
+ * The work runs over batches of a fixed number of segments, set at cm2_psd_create from L and
+ * max_work_bytes (<= 0: 512 MB; the batch is at least one segment, whatever the cap), so that the
+ * result of a block does not depend on the other blocks of the call: bit-equal to the same block
+ * estimated alone.  Overwrites d_psd; synchronises.  One handle must not run two calls at once.
+ * cm2_psd_info: h_info[3] = L, segments per batch, workspace bytes of the handle. */
+typedef struct cm2_psd cm2_psd;
+int cm2_psd_create(cm2_psd **out, int64_t nperseg, int detrend, int64_t max_work_bytes, void *stream);
+int cm2_psd_destroy(cm2_psd *p);
+int cm2_psd_info(const cm2_psd *p, int64_t *h_info);
+int cm2_psd_welch(cm2_psd *p, const double *d_tod, const int64_t *h_sizes, int64_t nb,
+                  double fsample, double *d_psd, void *stream);
+/* d_bands[b][0..lambda-1] (1 <= lambda <= L/2) from the one-sided PSD d_psd[b][0..L/2]:
+ * S_k = P_k fs / m_k (m_k = 1 at k = 0 and L/2, else 2), S_0 := S_1, G = 1/S,
+ * c_j = irfft(G, L)[j] as a cosine sum over k in increasing order, a_j = (1 - j/lambda) c_j (Bartlett:
+ * the band's symbol is G smoothed by the Fejer kernel, so every block is SPD).  A bin with S <= 0 or
+ * not finite fails with CM2_ERR_ARGUMENT and a message naming the block and the bin (the first in
+ * block-major order).  Overwrites d_bands; synchronises. */
+int cm2_noise_bands_from_psd(const double *d_psd, int64_t nb, int64_t nperseg, double fsample,
+                             int64_t lambda, double *d_bands, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
