@@ -2,16 +2,33 @@
 // permutations) and cm2_tiles_fixed.hip (fixed-order P^T)
 #pragma once
 #include "cm2_pixindex.h"
+#include "cm2_plan_policy.h"
 
 #include <vector>
 
-constexpr int64_t kHotTileMin = 32768;   // samples that make a one-pixel tile a hot tile (cm2_tiles_fixed.hip)
+namespace cm2 {
+// The switches that steer a tile plan and its fixed-order P^T lists.  Read from the environment ONCE,
+// by cm2_tiles_create (read_plan_switches, cm2_tiles.hip), and kept in the plan: lists that are
+// built later (cm2_tiles_prepare_pt, the first P^T) follow the switches of the plan's creation.
+struct PlanSwitches {
+    int pt_order = 1;            // CM2_PT_ORDER: atomic = 0, exact = 2, fixed or anything else = 1 (default)
+    bool tile_sort = false;      // CM2_TILE_BUILD=sort: radix sort + gather instead of the multisplit
+    policy::Balance balance = policy::Balance::automatic;   // CM2_TILE_BALANCE: parts | cut or a non-zero
+                                 // number = cut | anything else (0) = off; not set = automatic
+    bool full_angles = false;    // CM2_TILE_ANGLES=full: cos and sin arrays, no half-angle storage
+    bool fx_serial = false;      // CM2_FX_BUILD=serial: the reference builders of the lists (global tile order only)
+    int pt_slice = 0;            // CM2_PT_SLICE=<samples in [64, 2048]>: fixes the slice length (0: tuned)
+    int pt_parts = -1;           // CM2_PT_PARTS: 0 = one workgroup per tile, <samples> fixes the part length (-1: chosen)
+    bool pt_fuse = true;         // CM2_PT_FUSE=0 (or no number): hot ranges and part copies in kernels of their own
+};
+}  // namespace cm2
 
 struct cm2_tiles {
+    cm2::PlanSwitches sw;
     int64_t nt = 0, npix = 0, nvalid = 0;
     int pol = 0;
     int tp = 0;                  // pixels per tile (the largest width when the tiles are balanced)
-    bool balanced = false;       // tiles re-cut to equal sample counts (uneven hit map)
+    bool balanced = false;       // the tiles are not the uniform grid: boundaries are read from tile_p0
     std::vector<int64_t> tile_p0;   // [ntiles+1] first pixel of every tile (host)
     int64_t *d_tile_p0 = nullptr;
     int64_t ntiles = 0, nitems = 0;
@@ -98,6 +115,5 @@ void fx_free(cm2_tiles *t);
 int64_t fx_designed_bytes(const cm2_tiles *t);
 int fx_parts_info(const cm2_tiles *t, int64_t *h_info);   // cm2_tiles_pt_parts
 int fx_max_slice(const cm2_tiles *t);      // longest slice (samples) the fixed-order kernel's LDS budget allows
-bool fx_serial_build();                    // CM2_FX_BUILD=serial (the reference builders: global tile order only)
 }  // namespace cm2
 

@@ -34,6 +34,7 @@
 
 #include <hipcub/hipcub.hpp>
 #include <cstring>
+#include <type_traits>
 
 using namespace cm2;
 
@@ -605,7 +606,17 @@ __global__ __launch_bounds__(256) void k_perm_unpack(int64_t total, const uint64
 
 
 // ------------------------------------------------------------------ C ABI -------
-extern "C" int cm2_tiles_destroy(cm2_tiles *t);
+// f(std::integral_constant<int, POL>, std::bool_constant<HALF>) for the storage form of the plan: pol 1,
+// pol 2 and 3 with half or full angles (the five instances of the <POL, HALF> kernels)
+template <typename F>
+static int with_pol_half(const cm2_tiles *t, F &&f)
+{
+    using std::integral_constant;
+    if (t->pol == 1) return f(integral_constant<int, 1>{}, std::false_type{});
+    if (t->pol == 2)
+        return t->half ? f(integral_constant<int, 2>{}, std::true_type{}) : f(integral_constant<int, 2>{}, std::false_type{});
+    return t->half ? f(integral_constant<int, 3>{}, std::true_type{}) : f(integral_constant<int, 3>{}, std::false_type{});
+}
 
 extern "C" int cm2_tiles_destroy(cm2_tiles *t)
 {
@@ -616,6 +627,154 @@ extern "C" int cm2_tiles_destroy(cm2_tiles *t)
         if (q) (void)cm2::dev_free(q);
     cm2::fx_free(t);
     delete t;
+    return 0;
+}
+
+// The one place where the environment steers a tile plan (the values: PlanSwitches, cm2_tiles.h).
+static PlanSwitches read_plan_switches()
+{
+    PlanSwitches sw;
+    auto is = [](const char *e, const char *v) { return e && strcmp(e, v) == 0; };
+    if (const char *e = getenv("CM2_PT_ORDER")) sw.pt_order = is(e, "atomic") ? 0 : (is(e, "exact") ? 2 : 1);
+    sw.tile_sort = is(getenv("CM2_TILE_BUILD"), "sort");
+    if (const char *e = getenv("CM2_TILE_BALANCE"))
+        sw.balance = is(e, "parts") ? policy::Balance::parts
+                                    : (is(e, "cut") || atoi(e) != 0 ? policy::Balance::cut : policy::Balance::off);
+    sw.full_angles = is(getenv("CM2_TILE_ANGLES"), "full");
+    sw.fx_serial = is(getenv("CM2_FX_BUILD"), "serial");
+    if (const char *e = getenv("CM2_PT_SLICE")) sw.pt_slice = atoi(e);
+    if (const char *e = getenv("CM2_PT_PARTS")) sw.pt_parts = atoi(e);
+    if (const char *e = getenv("CM2_PT_FUSE")) sw.pt_fuse = atoi(e) != 0;
+    return sw;
+}
+
+// Stable partition of the samples by tile.  Default: the multisplit above (k_tile_rank, one scan,
+// k_tile_place).  With more tiles than its LDS histograms hold, or CM2_TILE_BUILD=sort: a radix sort of
+// (tile, time) pairs and a gather (k_tile_fill).  Same addresses either way.  Owns the temporaries of both
+// paths: run() partitions by the plan's current tiles (again after a re-cut), place() writes the plan's
+// per-sample arrays from what the last run left.
+struct Partition {
+    cm2_tiles *t;
+    const int32_t *d_pix;
+    hipStream_t stream;
+    int64_t nchunks;                                           // chunks of kSplitChunk samples
+    DevTemp<uint32_t> keys_in, keys_out, vals_in, tb_src;      // sort path
+    DevTemp<uint32_t> packed, cnt_t;                           // multisplit: tile << 16 | rank; counts -> bases
+    DevTemp<int64_t> d_off;
+    DevTemp<char> d_temp;
+    DevTemp<unsigned int> d_bad;                               // a pixel index outside [-1, npix) was seen
+    std::vector<int64_t> off;                                  // first address of every tile
+    bool sorted = false;                                       // which path the last run took
+
+    int sort(const int64_t *d_p0)
+    {
+        const int64_t nt = t->nt;
+        if (!keys_in.p) {
+            CM2_HIP(keys_in.alloc(nt));
+            CM2_HIP(keys_out.alloc(nt));
+            CM2_HIP(vals_in.alloc(nt));
+            CM2_HIP(tb_src.alloc(nt));
+        }
+        k_tile_keys<<<grid_for(nt), kBlock, 0, stream>>>(d_pix, nt, t->tp, d_p0, (uint32_t)t->ntiles, t->npix,
+                                                         keys_in, vals_in, d_bad);
+        CM2_LAUNCH_OK();
+        int end_bit = 1;
+        while (((int64_t)1 << end_bit) <= t->ntiles) ++end_bit;
+        size_t tb = 0;
+        CM2_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, keys_in.p, keys_out.p, vals_in.p,
+                                                   tb_src.p, nt, 0, end_bit, stream));
+        d_temp.release();
+        CM2_HIP(d_temp.alloc(tb + 16));
+        CM2_HIP(hipcub::DeviceRadixSort::SortPairs(d_temp.p, tb, keys_in.p, keys_out.p, vals_in.p,
+                                                   tb_src.p, nt, 0, end_bit, stream));
+        k_tile_bounds<<<(int)((t->ntiles + 1 + kBlock - 1) / kBlock), kBlock, 0, stream>>>(
+            keys_out, nt, t->ntiles, d_off);
+        CM2_LAUNCH_OK();
+        return 0;
+    }
+
+    int split(const int64_t *d_p0)
+    {
+        const int64_t ncnt = t->ntiles * nchunks + 1;          // (+1: the scan's last word = nvalid)
+        if (!packed.p) CM2_HIP(packed.alloc(t->nt));
+        cnt_t.release();
+        CM2_HIP(cnt_t.alloc(ncnt));
+        CM2_HIP(hipMemsetAsync(cnt_t.p, 0, sizeof(uint32_t) * ncnt, stream));
+        const size_t lds = sizeof(uint16_t) * 4 * (size_t)t->ntiles;
+        static size_t granted[64] = {0};
+        CM2_HIP(ensure_dynamic_lds((const void *)k_tile_rank, lds, granted));
+        k_tile_rank<<<(unsigned)((nchunks + 3) / 4), 256, lds, stream>>>(
+            d_pix, t->nt, t->tp, d_p0, (uint32_t)t->ntiles, t->npix, nchunks, packed, cnt_t, d_bad);
+        CM2_LAUNCH_OK();
+        CM2_CHECK(ncnt < ((int64_t)1 << 31), "cm2_tiles_create: %lld tile x chunk counts", (long long)ncnt);
+        size_t tb = 0;
+        CM2_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, cnt_t.p, cnt_t.p, (int)ncnt, stream));
+        d_temp.release();
+        CM2_HIP(d_temp.alloc(tb + 16));
+        CM2_HIP(hipcub::DeviceScan::ExclusiveSum(d_temp.p, tb, cnt_t.p, cnt_t.p, (int)ncnt, stream));
+        k_tile_offsets<<<(int)((t->ntiles + 1 + kBlock - 1) / kBlock), kBlock, 0, stream>>>(cnt_t, nchunks,
+                                                                                            t->ntiles, d_off);
+        CM2_LAUNCH_OK();
+        return 0;
+    }
+
+    // d_p0: the tiles' first pixels on the device (nullptr: uniform tiles of t->tp pixels)
+    int run(const int64_t *d_p0)
+    {
+        if (!d_bad.p) {
+            CM2_HIP(d_bad.alloc(1));
+            CM2_HIP(hipMemsetAsync(d_bad, 0, sizeof(unsigned int), stream));
+        }
+        d_off.release();
+        sorted = t->sw.tile_sort || t->ntiles > kSplitMaxTiles || t->ntiles * nchunks + 1 >= ((int64_t)1 << 31);
+        CM2_HIP(d_off.alloc(t->ntiles + 1));
+        if (int rc = sorted ? sort(d_p0) : split(d_p0)) return rc;
+        off.assign((size_t)t->ntiles + 1, 0);
+        CM2_HIP(cm2::download(off.data(), d_off, sizeof(int64_t) * (t->ntiles + 1), stream));
+        CM2_HIP(hipStreamSynchronize(stream));
+        return 0;
+    }
+
+    int place(const double *d_cos, const double *d_sin)
+    {
+        const int64_t nt = t->nt;
+        const int64_t *d_p0 = t->balanced ? t->d_tile_p0 : nullptr;
+        return with_pol_half(t, [&](auto pol_c, auto half_c) -> int {
+            constexpr int POL = decltype(pol_c)::value;
+            constexpr bool HALF = decltype(half_c)::value;
+            if (sorted)
+                k_tile_fill<POL, HALF><<<grid_for(nt), kBlock, 0, stream>>>(
+                    nt, t->nvalid, t->tp, d_p0, (uint32_t)t->ntiles, tb_src, d_pix, d_cos, d_sin, t->d_tb_dst,
+                    t->d_pl, HALF ? t->d_half : t->d_cos, t->d_sin);
+            else if ((HALF || POL == 1) && t->ntiles <= 4096) {
+                const size_t lds = (POL > 1 ? sizeof(double) * kSplitChunk : 0) +
+                                   sizeof(uint32_t) * (2 * (size_t)t->ntiles + 1) + sizeof(uint16_t) * 2 * kSplitChunk;
+                static size_t granted[64] = {0};
+                CM2_HIP(ensure_dynamic_lds((const void *)k_tile_place_staged<POL>, lds, granted));
+                k_tile_place_staged<POL><<<(unsigned)nchunks, 256, lds, stream>>>(
+                    nt, t->tp, d_p0, (int)t->ntiles, packed, cnt_t, d_pix, d_cos, d_sin, t->d_tb_dst, t->d_pl,
+                    t->d_half);
+            } else
+                k_tile_place<POL, HALF><<<grid_for(nt), kBlock, 0, stream>>>(
+                    nt, t->tp, d_p0, packed, cnt_t, d_pix, d_cos, d_sin, t->d_tb_dst, t->d_pl,
+                    HALF ? t->d_half : t->d_cos, t->d_sin);
+            CM2_LAUNCH_OK();
+            return 0;
+        });
+    }
+};
+
+// hits of every pixel on the host (input of the policy's re-cuts); d_hits: the caller's temporary
+static int pixel_hits(const int32_t *d_pix, int64_t nt, int64_t npix, hipStream_t stream,
+                      DevTemp<unsigned int> &d_hits, std::vector<unsigned int> &hits)
+{
+    CM2_HIP(d_hits.alloc(npix));
+    CM2_HIP(hipMemsetAsync(d_hits, 0, sizeof(unsigned int) * npix, stream));
+    k_pix_hist<<<grid_for(nt), kBlock, 0, stream>>>(d_pix, nt, npix, d_hits);
+    CM2_LAUNCH_OK();
+    hits.resize((size_t)npix);
+    CM2_HIP(cm2::download(hits.data(), d_hits, sizeof(unsigned int) * npix, stream));
+    CM2_HIP(hipStreamSynchronize(stream));
     return 0;
 }
 
@@ -636,225 +795,56 @@ extern "C" int cm2_tiles_create(cm2_tiles **out, const int32_t *d_pix, const dou
     cm2_tiles *t = new cm2_tiles();
     struct Guard { cm2_tiles *t; ~Guard() { if (t) cm2_tiles_destroy(t); } } guard{t};
     t->nt = nt; t->npix = npix; t->pol = pol; t->tp = tile_pixels;
-    t->ntiles = (npix + tile_pixels - 1) / tile_pixels;
     t->plan_id = next_plan_id();
-    // order of the per-pixel sums of P^T: fixed (time order, reproducible; default) or atomic
-    if (const char *e = getenv("CM2_PT_ORDER"))          // atomic | exact | fixed (default)
-        t->pt_fixed = !strcmp(e, "atomic") ? 0 : (!strcmp(e, "exact") ? 2 : 1);
+    t->sw = read_plan_switches();
+    // order of the per-pixel sums of P^T: fixed (time order, reproducible; default), exact or atomic
+    t->pt_fixed = t->sw.pt_order;
     if (cm2::exact_order_setting() >= 0 && t->pt_fixed) t->pt_fixed = cm2::exact_order_setting() ? 2 : 1;
 
-    // Stable partition of the samples by tile.  Default: the multisplit above (k_tile_rank, one
-    // scan, k_tile_place).  With more tiles than its LDS histograms hold, or CM2_TILE_BUILD=sort:
-    // a radix sort of (tile, time) pairs and a gather (k_tile_fill).  Same addresses either way.
-    bool use_sort = false;
-    if (const char *e = getenv("CM2_TILE_BUILD")) use_sort = strcmp(e, "sort") == 0;
-    DevTemp<uint32_t> keys_in, keys_out, vals_in, tb_src;      // sort path
-    DevTemp<uint32_t> packed, cnt_t;                           // multisplit: tile << 16 | rank; counts -> bases
-    const int64_t nchunks = (nt + kSplitChunk - 1) / kSplitChunk;
-    DevTemp<int64_t> d_off;
-    DevTemp<char> d_temp;
-    DevTemp<unsigned int> d_bad;
-    CM2_HIP(d_bad.alloc(1));
-    CM2_HIP(hipMemsetAsync(d_bad, 0, sizeof(unsigned int), stream));
-    std::vector<int64_t> off;
-    bool sorted = false;                                       // which path the last partition took
-    auto partition_sort = [&](const int64_t *d_p0) -> int {
-        if (!keys_in.p) {
-            CM2_HIP(keys_in.alloc(nt));
-            CM2_HIP(keys_out.alloc(nt));
-            CM2_HIP(vals_in.alloc(nt));
-            CM2_HIP(tb_src.alloc(nt));
-        }
-        k_tile_keys<<<grid_for(nt), kBlock, 0, stream>>>(d_pix, nt, tile_pixels, d_p0,
-                                                         (uint32_t)t->ntiles, npix, keys_in, vals_in,
-                                                         d_bad);
-        CM2_LAUNCH_OK();
-        int end_bit = 1;
-        while (((int64_t)1 << end_bit) <= t->ntiles) ++end_bit;
-        size_t tb = 0;
-        CM2_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, keys_in.p, keys_out.p, vals_in.p,
-                                                   tb_src.p, nt, 0, end_bit, stream));
-        d_temp.release();
-        CM2_HIP(d_temp.alloc(tb + 16));
-        CM2_HIP(hipcub::DeviceRadixSort::SortPairs(d_temp.p, tb, keys_in.p, keys_out.p, vals_in.p,
-                                                   tb_src.p, nt, 0, end_bit, stream));
-        k_tile_bounds<<<(int)((t->ntiles + 1 + kBlock - 1) / kBlock), kBlock, 0, stream>>>(
-            keys_out, nt, t->ntiles, d_off);
-        CM2_LAUNCH_OK();
-        return 0;
-    };
-    auto partition_split = [&](const int64_t *d_p0) -> int {
-        const int64_t ncnt = t->ntiles * nchunks + 1;          // (+1: the scan's last word = nvalid)
-        if (!packed.p) CM2_HIP(packed.alloc(nt));
-        cnt_t.release();
-        CM2_HIP(cnt_t.alloc(ncnt));
-        CM2_HIP(hipMemsetAsync(cnt_t.p, 0, sizeof(uint32_t) * ncnt, stream));
-        const size_t lds = sizeof(uint16_t) * 4 * (size_t)t->ntiles;
-        static size_t granted[64] = {0};
-        CM2_HIP(ensure_dynamic_lds((const void *)k_tile_rank, lds, granted));
-        k_tile_rank<<<(unsigned)((nchunks + 3) / 4), 256, lds, stream>>>(
-            d_pix, nt, tile_pixels, d_p0, (uint32_t)t->ntiles, npix, nchunks, packed, cnt_t, d_bad);
-        CM2_LAUNCH_OK();
-        CM2_CHECK(ncnt < ((int64_t)1 << 31), "cm2_tiles_create: %lld tile x chunk counts", (long long)ncnt);
-        size_t tb = 0;
-        CM2_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, cnt_t.p, cnt_t.p, (int)ncnt, stream));
-        d_temp.release();
-        CM2_HIP(d_temp.alloc(tb + 16));
-        CM2_HIP(hipcub::DeviceScan::ExclusiveSum(d_temp.p, tb, cnt_t.p, cnt_t.p, (int)ncnt, stream));
-        k_tile_offsets<<<(int)((t->ntiles + 1 + kBlock - 1) / kBlock), kBlock, 0, stream>>>(cnt_t, nchunks,
-                                                                                            t->ntiles, d_off);
-        CM2_LAUNCH_OK();
-        return 0;
-    };
-    // `off`: first address of every tile
-    auto partition = [&](const int64_t *d_p0) -> int {
-        d_off.release();
-        sorted = use_sort || t->ntiles > kSplitMaxTiles || t->ntiles * nchunks + 1 >= ((int64_t)1 << 31);
-        CM2_HIP(d_off.alloc(t->ntiles + 1));
-        if (int rc = sorted ? partition_sort(d_p0) : partition_split(d_p0)) return rc;
-        off.assign((size_t)t->ntiles + 1, 0);
-        CM2_HIP(cm2::download(off.data(), d_off, sizeof(int64_t) * (t->ntiles + 1), stream));
-        CM2_HIP(hipStreamSynchronize(stream));
-        return 0;
-    };
-    if (int rc = partition(nullptr)) return rc;
+    // uniform tiles first: their loads decide the tiling
+    t->tile_p0 = policy::uniform_tiles(npix, tile_pixels);
+    t->ntiles = (int64_t)t->tile_p0.size() - 1;
+    Partition part{t, d_pix, stream, (nt + kSplitChunk - 1) / kSplitChunk};
+    if (int rc = part.run(nullptr)) return rc;
     unsigned int h_bad = 0;
-    CM2_HIP(cm2::download(&h_bad, d_bad, sizeof(h_bad), nullptr));
+    CM2_HIP(cm2::download(&h_bad, part.d_bad, sizeof(h_bad), nullptr));
     CM2_CHECK(h_bad == 0, "cm2_tiles_create: a pixel index is outside [-1, npix=%lld)",
               (long long)npix);
-    t->tile_p0.assign((size_t)t->ntiles + 1, 0);
-    for (int64_t b = 0; b <= t->ntiles; ++b)
-        t->tile_p0[(size_t)b] = b * tile_pixels < npix ? b * tile_pixels : npix;
-    // The fixed-order P^T gives every tile to ONE workgroup: a hit map that is far from uniform
-    // (half of the samples on a tenth of the sky: 0.47 -> 1.7 ms) would leave most of the chip
-    // waiting for the heaviest tiles.  When some uniform tile holds over 25 % more than the mean,
-    // the pixel ranges are re-cut to equal sample counts (width <= tile_pixels): every pixel is
-    // still summed by one workgroup in time order, so results do not change by a bit.
-    // Round 4: by default such a hit map keeps the uniform tile width instead, and the fixed-order P^T
-    // shares the slices of its heavy tiles out to several workgroups (pt_split; cm2_tiles.h, "PARTS"):
-    // narrow dense tiles see many hits per pixel and slice (runs of 5-8 list entries in two level
-    // passes) and halve the address runs of the overlap-save kernel.  Only a pixel heavy enough for
-    // the hot-tile path is cut out as a tile of its own.  CM2_TILE_BALANCE: 0 = uniform tiles, one
-    // workgroup each; 1 / cut = the equal-load cut (also chosen when the exact summation order is
-    // asked for: it does not change a bit); parts = split even when the hit map is even.
-    const char *bal = getenv("CM2_TILE_BALANCE");
-    bool balance = false, split = false;
-    double mean_load = 0.0;
-    {
-        int64_t nmax = 0;
-        for (int64_t b = 0; b < t->ntiles; ++b)
-            if (off[(size_t)b + 1] - off[(size_t)b] > nmax) nmax = off[(size_t)b + 1] - off[(size_t)b];
-        mean_load = (double)off[(size_t)t->ntiles] / (double)(t->ntiles > 0 ? t->ntiles : 1);
-        const bool uneven = t->ntiles >= 64 && off[(size_t)t->ntiles] >= (1 << 20) && (double)nmax > 1.25 * mean_load;
-        const bool some = off[(size_t)t->ntiles] > 0;
-        if (!bal) {
-            balance = uneven && t->pt_fixed == 2;      // (CM2_PT_ORDER=exact / cm2_set_exact_order(1), read above)
-            split = uneven && !balance;
-        } else if (strcmp(bal, "parts") == 0) {
-            split = some;
-        } else if (strcmp(bal, "cut") == 0 || atoi(bal) != 0) {
-            balance = some;
-        }
-    }
-    t->pt_split = split;
+    const policy::TilingChoice choice = policy::choose_tiling(part.off, t->pt_fixed == 2, t->sw.balance);
+    t->pt_split = choice.pt_split;
     DevTemp<int64_t> d_p0;
-    if (balance) {
+    {
+        std::vector<int64_t> p0v;                           // re-cut boundaries (empty: the uniform tiles stay)
         DevTemp<unsigned int> d_hits;
-        CM2_HIP(d_hits.alloc(npix));
-        CM2_HIP(hipMemsetAsync(d_hits, 0, sizeof(unsigned int) * npix, stream));
-        k_pix_hist<<<grid_for(nt), kBlock, 0, stream>>>(d_pix, nt, npix, d_hits);
-        CM2_LAUNCH_OK();
-        std::vector<unsigned int> hits((size_t)npix);
-        CM2_HIP(cm2::download(hits.data(), d_hits, sizeof(unsigned int) * npix, stream));
-        CM2_HIP(hipStreamSynchronize(stream));
-        // as many tiles as before would have had at equal load, 2 % slack so that rounding does
-        // not spill a 513th tile; a tile ends when the next pixel would exceed the target or the
-        // width tile_pixels (a single pixel heavier than the target is a tile of its own)
-        const int64_t nvalid = off[(size_t)t->ntiles];
-        // cuts every rank of a sharded run has in common, whatever its own hit map: the group
-        // boundaries of cm2_tiles_group_tiles (the pieces of the map that are all-reduced while
-        // the next piece is back-projected) -- the uniform tiling's tile boundaries nearest to
-        // eighths of the map, a function of npix and tile_pixels alone
-        const int64_t ntu = (npix + tile_pixels - 1) / tile_pixels;
-        int64_t forced[9];
-        for (int c = 0; c <= 8; ++c) {
-            forced[c] = (ntu * c / 8) * tile_pixels;
-            if (forced[c] > npix || c == 8) forced[c] = npix;
-        }
-        // The fixed-order P^T keeps 512 workgroups resident (two per CU): tiles of equal load
-        // finish in whole rounds of 512, so 737 tiles cost as much as 1024.  The width limit makes
-        // a sparse region take more tiles than its load asks for; the target load is therefore
-        // lowered (n = 1, 2, 3, 4 times the uniform count) until the cut fits n x the uniform
-        // count, with 2 % slack so that rounding does not spill one more tile; a tile ends when the
-        // next pixel would exceed the target or the width tile_pixels (a single pixel heavier than
-        // the target is a tile of its own).
-        std::vector<int64_t> p0v;
-        const int64_t base = t->ntiles;
-        for (int mult = 1; mult <= 4; ++mult) {
-            const int64_t target = (int64_t)(1.02 * (double)nvalid / (double)(base * mult)) + 1;
-            int fc = 1;
-            p0v.assign(1, 0);
-            int64_t acc = 0, start = 0;
-            for (int64_t p = 0; p < npix; ++p) {
-                const int64_t h = hits[(size_t)p];
-                while (fc < 8 && forced[fc] < p) ++fc;
-                const bool at_cut = fc < 8 && forced[fc] == p;
-                if (p > start && (acc + h > target || p - start >= tile_pixels || at_cut)) {
-                    p0v.push_back(p);
-                    start = p;
-                    acc = 0;
-                }
-                acc += h;
-            }
-            p0v.push_back(npix);
-            if ((int64_t)p0v.size() - 1 <= base * mult || base % 512 != 0) break;
-        }
-        t->ntiles = (int64_t)p0v.size() - 1;
-        t->tile_p0 = p0v;
-        CM2_HIP(d_p0.alloc(p0v.size()));
-        CM2_HIP(cm2::upload(d_p0.p, p0v.data(), sizeof(int64_t) * p0v.size(), nullptr));
-        if (int rc = partition(d_p0.p)) return rc;
-    }
-    if (split) {
-        int64_t nmax = 0;
-        for (int64_t b = 0; b < t->ntiles; ++b)
-            if (off[(size_t)b + 1] - off[(size_t)b] > nmax) nmax = off[(size_t)b + 1] - off[(size_t)b];
-        const int64_t hot_min = (int64_t)(0.5 * mean_load) > kHotTileMin ? (int64_t)(0.5 * mean_load) : kHotTileMin;
-        if (nmax >= hot_min) {                              // (otherwise no pixel can be that heavy)
-            DevTemp<unsigned int> d_hits;
-            CM2_HIP(d_hits.alloc(npix));
-            CM2_HIP(hipMemsetAsync(d_hits, 0, sizeof(unsigned int) * npix, stream));
-            k_pix_hist<<<grid_for(nt), kBlock, 0, stream>>>(d_pix, nt, npix, d_hits);
-            CM2_LAUNCH_OK();
-            std::vector<unsigned int> hits((size_t)npix);
-            CM2_HIP(cm2::download(hits.data(), d_hits, sizeof(unsigned int) * npix, stream));
-            CM2_HIP(hipStreamSynchronize(stream));
-            std::vector<int64_t> p0v(1, 0);
+        std::vector<unsigned int> hits;
+        if (choice.tiling == policy::Tiling::equal_load) {
+            if (int rc = pixel_hits(d_pix, nt, npix, stream, d_hits, hits)) return rc;
+            p0v = policy::equal_load_tiles(hits, npix, tile_pixels, t->ntiles, part.off[(size_t)t->ntiles]);
+        } else if (choice.hot_min > 0) {
+            if (int rc = pixel_hits(d_pix, nt, npix, stream, d_hits, hits)) return rc;
             bool any = false;
-            for (int64_t p = 1; p < npix; ++p) {
-                const bool hot_here = (int64_t)hits[(size_t)p] >= hot_min, hot_before = (int64_t)hits[(size_t)p - 1] >= hot_min;
-                if (p % tile_pixels == 0 || hot_here || hot_before) p0v.push_back(p);
-                any = any || hot_here || hot_before;
-            }
-            p0v.push_back(npix);
-            if (any) {
-                t->ntiles = (int64_t)p0v.size() - 1;
-                t->tile_p0 = p0v;
-                CM2_HIP(d_p0.alloc(p0v.size()));
-                CM2_HIP(cm2::upload(d_p0.p, p0v.data(), sizeof(int64_t) * p0v.size(), nullptr));
-                if (int rc = partition(d_p0.p)) return rc;
-                balance = true;                             // (the kernels below read the re-cut boundaries)
-            }
+            p0v = policy::hot_pixel_tiles(hits, npix, tile_pixels, choice.hot_min, &any);
+            if (!any) p0v.clear();
+        }
+        // balanced = "the tiles are not the uniform grid", whichever rule re-cut them: the kernels then find a
+        // pixel's tile in d_tile_p0, and only the shared cuts (policy::shared_cuts) are boundaries for sure
+        t->balanced = !p0v.empty();
+        if (t->balanced) {
+            t->ntiles = (int64_t)p0v.size() - 1;
+            t->tile_p0 = p0v;
+            CM2_HIP(d_p0.alloc(p0v.size()));
+            CM2_HIP(cm2::upload(d_p0.p, p0v.data(), sizeof(int64_t) * p0v.size(), nullptr));
+            if (int rc = part.run(d_p0.p)) return rc;
         }
     }
-    t->balanced = balance;
+    const std::vector<int64_t> &off = part.off;
     CM2_HIP(cm2::dev_malloc(&t->d_tile_p0, sizeof(int64_t) * (t->ntiles + 1)));
     CM2_HIP(cm2::upload(t->d_tile_p0, t->tile_p0.data(), sizeof(int64_t) * (t->ntiles + 1), nullptr));
     t->nvalid = off[t->ntiles];
     t->tile_count.assign((size_t)t->ntiles, 0);
     for (int64_t b = 0; b < t->ntiles; ++b) t->tile_count[(size_t)b] = off[(size_t)b + 1] - off[(size_t)b];
     t->tile_off = off;
-    t->d_tile_off = d_off.keep();
+    t->d_tile_off = part.d_off.keep();
 
     const int64_t nv = t->nvalid > 0 ? t->nvalid : 1;
     CM2_HIP(cm2::dev_malloc(&t->d_tb_dst, sizeof(uint32_t) * nt));
@@ -862,19 +852,16 @@ extern "C" int cm2_tiles_create(cm2_tiles **out, const int32_t *d_pix, const dou
     // half-angle storage (one double per sample instead of cos and sin) when every pair lies
     // on the unit circle; CM2_TILE_ANGLES=full keeps both arrays
     t->half = false;
-    if (pol > 1 && nt > 0 && tile_pixels <= 0x8000) {
-        const char *e = getenv("CM2_TILE_ANGLES");
-        if (!(e && strcmp(e, "full") == 0)) {
-            DevTemp<unsigned int> d_off_circle;
-            CM2_HIP(d_off_circle.alloc(1));
-            CM2_HIP(hipMemsetAsync(d_off_circle, 0, sizeof(unsigned int), stream));
-            k_unit_circle<<<grid_for(nt), kBlock, 0, stream>>>(nt, d_cos, d_sin, d_off_circle);
-            CM2_LAUNCH_OK();
-            unsigned int h_off = 0;
-            CM2_HIP(cm2::download(&h_off, d_off_circle, sizeof(h_off), stream));
-            CM2_HIP(hipStreamSynchronize(stream));
-            t->half = (h_off == 0);
-        }
+    if (pol > 1 && nt > 0 && tile_pixels <= 0x8000 && !t->sw.full_angles) {
+        DevTemp<unsigned int> d_off_circle;
+        CM2_HIP(d_off_circle.alloc(1));
+        CM2_HIP(hipMemsetAsync(d_off_circle, 0, sizeof(unsigned int), stream));
+        k_unit_circle<<<grid_for(nt), kBlock, 0, stream>>>(nt, d_cos, d_sin, d_off_circle);
+        CM2_LAUNCH_OK();
+        unsigned int h_off = 0;
+        CM2_HIP(cm2::download(&h_off, d_off_circle, sizeof(h_off), stream));
+        CM2_HIP(hipStreamSynchronize(stream));
+        t->half = (h_off == 0);
     }
     if (pol > 1) {
         if (t->half) {
@@ -884,60 +871,19 @@ extern "C" int cm2_tiles_create(cm2_tiles **out, const int32_t *d_pix, const dou
             CM2_HIP(cm2::dev_malloc(&t->d_sin, sizeof(double) * nv));
         }
     }
-    auto place = [&]() -> int {
-#define CM2_TF(POL, HALF)                                                                      \
-    do {                                                                                       \
-        if (sorted)                                                                            \
-            k_tile_fill<POL, HALF><<<grid_for(nt), kBlock, 0, stream>>>(                       \
-                nt, t->nvalid, tile_pixels, balance ? t->d_tile_p0 : nullptr,                  \
-                (uint32_t)t->ntiles, tb_src, d_pix, d_cos, d_sin, t->d_tb_dst, t->d_pl,        \
-                HALF ? t->d_half : t->d_cos, t->d_sin);                                        \
-        else if ((HALF || POL == 1) && t->ntiles <= 4096) {                                    \
-            const size_t lds = (POL > 1 ? sizeof(double) * kSplitChunk : 0) +                  \
-                               sizeof(uint32_t) * (2 * (size_t)t->ntiles + 1) +                \
-                               sizeof(uint16_t) * 2 * kSplitChunk;                             \
-            static size_t granted[64] = {0};                                                   \
-            CM2_HIP(ensure_dynamic_lds((const void *)k_tile_place_staged<POL>, lds, granted));  \
-            k_tile_place_staged<POL><<<(unsigned)nchunks, 256, lds, stream>>>(                 \
-                nt, tile_pixels, balance ? t->d_tile_p0 : nullptr, (int)t->ntiles,             \
-                packed, cnt_t, d_pix, d_cos, d_sin, t->d_tb_dst, t->d_pl, t->d_half);          \
-        } else                                                                                 \
-            k_tile_place<POL, HALF><<<grid_for(nt), kBlock, 0, stream>>>(                      \
-                nt, tile_pixels, balance ? t->d_tile_p0 : nullptr, packed, cnt_t,              \
-                d_pix, d_cos, d_sin, t->d_tb_dst, t->d_pl, HALF ? t->d_half : t->d_cos,        \
-                t->d_sin);                                                                     \
-    } while (0)
-    if (pol == 1) CM2_TF(1, false);
-    else if (pol == 2) { if (t->half) CM2_TF(2, true); else CM2_TF(2, false); }
-    else { if (t->half) CM2_TF(3, true); else CM2_TF(3, false); }
-#undef CM2_TF
-    CM2_LAUNCH_OK();
-    return 0;
-    };
-    if (int rc = place()) return rc;
+    if (int rc = part.place(d_cos, d_sin)) return rc;
     // work items: every tile's bucket cut into address ranges of at most slice_samples (none for an empty one)
-    std::vector<int32_t> it_tile;
-    std::vector<int64_t> it_k0, it_k1;
-    t->tile_item0.assign((size_t)t->ntiles + 1, 0);
-    for (int64_t b = 0; b < t->ntiles; ++b) {
-        t->tile_item0[(size_t)b] = (int64_t)it_tile.size();
-        const int64_t a1 = off[(size_t)b + 1];
-        for (int64_t k = off[(size_t)b]; k < a1; k += slice_samples) {
-            it_tile.push_back((int32_t)b);
-            it_k0.push_back(k);
-            it_k1.push_back(k + slice_samples < a1 ? k + slice_samples : a1);
-        }
-    }
-    t->tile_item0[(size_t)t->ntiles] = (int64_t)it_tile.size();
-    t->nitems = (int64_t)it_tile.size();
+    const policy::WorkItems items = policy::work_items(off, slice_samples);
+    t->tile_item0 = items.tile_item0;
+    t->nitems = (int64_t)items.tile.size();
     const int64_t ni = t->nitems > 0 ? t->nitems : 1;
     CM2_HIP(cm2::dev_malloc(&t->d_item_tile, sizeof(int32_t) * ni));
     CM2_HIP(cm2::dev_malloc(&t->d_item_k0, sizeof(int64_t) * ni));
     CM2_HIP(cm2::dev_malloc(&t->d_item_k1, sizeof(int64_t) * ni));
     if (t->nitems) {
-        CM2_HIP(cm2::upload(t->d_item_tile, it_tile.data(), sizeof(int32_t) * ni, nullptr));
-        CM2_HIP(cm2::upload(t->d_item_k0, it_k0.data(), sizeof(int64_t) * ni, nullptr));
-        CM2_HIP(cm2::upload(t->d_item_k1, it_k1.data(), sizeof(int64_t) * ni, nullptr));
+        CM2_HIP(cm2::upload(t->d_item_tile, items.tile.data(), sizeof(int32_t) * ni, nullptr));
+        CM2_HIP(cm2::upload(t->d_item_k0, items.k0.data(), sizeof(int64_t) * ni, nullptr));
+        CM2_HIP(cm2::upload(t->d_item_k1, items.k1.data(), sizeof(int64_t) * ni, nullptr));
     }
     CM2_HIP(hipStreamSynchronize(stream));
     guard.t = nullptr;
@@ -985,21 +931,21 @@ extern "C" const int64_t *cm2_tiles_offsets(const cm2_tiles *t) { return t ? t->
 
 // Tile indices bounding `ngroups` consecutive groups of tiles whose PIXEL boundaries are the same on
 // every rank of a sharded run (ranks with different hit maps may have cut their tiles differently):
-// group g = tiles [h_tiles[g], h_tiles[g + 1]).
+// group g = tiles [h_tiles[g], h_tiles[g + 1]).  Up to 8 groups are bounded by policy::shared_cuts, the
+// uniform tiling's boundaries nearest to eighths of the map.
 extern "C" int cm2_tiles_group_tiles(const cm2_tiles *t, int ngroups, int64_t *h_tiles)
 {
     CM2_CHECK(t && h_tiles && ngroups >= 1, "cm2_tiles_group_tiles: bad argument");
-    const int64_t ntu = (t->npix + t->tp - 1) / t->tp;
+    const std::vector<int64_t> eighths = policy::shared_cuts(t->npix, t->tp);
     for (int g = 0; g <= ngroups; ++g) {
-        const int c = g == ngroups ? 8 : (ngroups <= 8 ? (8 * g) / ngroups : -1);
         int64_t pixel;
         if (ngroups > 8) {                     // finer than eighths: only a uniform tiling has the cuts
             CM2_CHECK(!t->balanced, "cm2_tiles_group_tiles: at most 8 groups on a balanced tiling");
-            pixel = (ntu * g / ngroups) * t->tp;
+            pixel = ((t->npix + t->tp - 1) / t->tp * g / ngroups) * t->tp;
+            if (pixel > t->npix || g == ngroups) pixel = t->npix;
         } else {
-            pixel = (ntu * c / 8) * t->tp;
+            pixel = eighths[(size_t)((8 * g) / ngroups)];
         }
-        if (pixel > t->npix || g == ngroups) pixel = t->npix;
         // the tile that starts at `pixel` (every tiling has a boundary there)
         int64_t lo = 0, hi = t->ntiles;
         while (lo < hi) {
@@ -1032,16 +978,31 @@ extern "C" int cm2_P_tiles_apply(const cm2_tiles *t, const double *d_x, double *
     if (t->nitems == 0) return 0;
     hipStream_t stream = as_stream(stream_);
     const size_t lds = sizeof(double) * t->tp * t->pol;
-#define CM2_PT(POL, HALF)                                                                      \
-    k_P_tiles<POL, HALF><<<(int)t->nitems, kPBlock, lds, stream>>>(                            \
-        t->d_tile_p0, t->d_item_tile, t->d_item_k0, t->d_item_k1, t->d_pl,                     \
-        HALF ? t->d_half : t->d_cos, t->d_sin, d_x, d_tod_tb)
-    if (t->pol == 1) CM2_PT(1, false);
-    else if (t->pol == 2) { if (t->half) CM2_PT(2, true); else CM2_PT(2, false); }
-    else { if (t->half) CM2_PT(3, true); else CM2_PT(3, false); }
-#undef CM2_PT
-    CM2_LAUNCH_OK();
-    return 0;
+    return with_pol_half(t, [&](auto pol_c, auto half_c) -> int {
+        constexpr int POL = decltype(pol_c)::value;
+        constexpr bool HALF = decltype(half_c)::value;
+        k_P_tiles<POL, HALF><<<(int)t->nitems, kPBlock, lds, stream>>>(
+            t->d_tile_p0, t->d_item_tile, t->d_item_k0, t->d_item_k1, t->d_pl,
+            HALF ? t->d_half : t->d_cos, t->d_sin, d_x, d_tod_tb);
+        CM2_LAUNCH_OK();
+        return 0;
+    });
+}
+
+// the atomic P^T of the work items [i0, i1)
+static int pt_tiles_atomic(const cm2_tiles *t, int64_t i0, int64_t i1, const double *d_tod_tb, double *d_out,
+                           hipStream_t stream)
+{
+    const size_t lds = sizeof(double) * t->tp * t->pol;
+    return with_pol_half(t, [&](auto pol_c, auto half_c) -> int {
+        constexpr int POL = decltype(pol_c)::value;
+        constexpr bool HALF = decltype(half_c)::value;
+        k_Pt_tiles<POL, HALF><<<(int)(i1 - i0), kPtBlock, lds, stream>>>(
+            t->d_tile_p0, t->d_item_tile + i0, t->d_item_k0 + i0, t->d_item_k1 + i0, t->d_pl,
+            HALF ? t->d_half : t->d_cos, t->d_sin, d_tod_tb, d_out);
+        CM2_LAUNCH_OK();
+        return 0;
+    });
 }
 
 extern "C" int cm2_Pt_tiles_apply(const cm2_tiles *t, const double *d_tod_tb, double *d_out,
@@ -1054,17 +1015,7 @@ extern "C" int cm2_Pt_tiles_apply(const cm2_tiles *t, const double *d_tod_tb, do
     if (fixed) return cm2::fx_launch(t, d_tod_tb, d_out, 0, t->ntiles, stream);
     CM2_HIP(hipMemsetAsync(d_out, 0, sizeof(double) * t->npix * t->pol, stream));
     if (t->nitems == 0) return 0;
-    const size_t lds = sizeof(double) * t->tp * t->pol;
-#define CM2_PTT(POL, HALF)                                                                     \
-    k_Pt_tiles<POL, HALF><<<(int)t->nitems, kPtBlock, lds, stream>>>(                          \
-        t->d_tile_p0, t->d_item_tile, t->d_item_k0, t->d_item_k1, t->d_pl,                     \
-        HALF ? t->d_half : t->d_cos, t->d_sin, d_tod_tb, d_out)
-    if (t->pol == 1) CM2_PTT(1, false);
-    else if (t->pol == 2) { if (t->half) CM2_PTT(2, true); else CM2_PTT(2, false); }
-    else { if (t->half) CM2_PTT(3, true); else CM2_PTT(3, false); }
-#undef CM2_PTT
-    CM2_LAUNCH_OK();
-    return 0;
+    return pt_tiles_atomic(t, 0, t->nitems, d_tod_tb, d_out, stream);
 }
 
 extern "C" int cm2_Pt_tiles_apply_range(const cm2_tiles *t, const double *d_tod_tb, double *d_out,
@@ -1083,17 +1034,7 @@ extern "C" int cm2_Pt_tiles_apply_range(const cm2_tiles *t, const double *d_tod_
     CM2_HIP(hipMemsetAsync(d_out + p0 * t->pol, 0, sizeof(double) * (p1 - p0) * t->pol, stream));
     const int64_t i0 = t->tile_item0[(size_t)tile_lo], i1 = t->tile_item0[(size_t)tile_hi];
     if (i1 == i0) return 0;
-    const size_t lds = sizeof(double) * t->tp * t->pol;
-#define CM2_PTR(POL, HALF)                                                                     \
-    k_Pt_tiles<POL, HALF><<<(int)(i1 - i0), kPtBlock, lds, stream>>>(                          \
-        t->d_tile_p0, t->d_item_tile + i0, t->d_item_k0 + i0, t->d_item_k1 + i0, t->d_pl,      \
-        HALF ? t->d_half : t->d_cos, t->d_sin, d_tod_tb, d_out)
-    if (t->pol == 1) CM2_PTR(1, false);
-    else if (t->pol == 2) { if (t->half) CM2_PTR(2, true); else CM2_PTR(2, false); }
-    else { if (t->half) CM2_PTR(3, true); else CM2_PTR(3, false); }
-#undef CM2_PTR
-    CM2_LAUNCH_OK();
-    return 0;
+    return pt_tiles_atomic(t, i0, i1, d_tod_tb, d_out, stream);
 }
 
 __global__ __launch_bounds__(256) void k_i32_time_to_tiles(int64_t nt,

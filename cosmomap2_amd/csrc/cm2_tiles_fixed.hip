@@ -504,7 +504,7 @@ __global__ __launch_bounds__(256) void k_parts_combine(const int64_t *__restrict
 // then adds the range sums of a tile in time order and writes the pixel.  Every boundary and every
 // order depends on the bucket's length only: reproducible bit for bit, independent of the rest of
 // the hit map; a regrouping of the serial sum, ~1e-16 relative per level away from it.
-constexpr int64_t kHotMin = kHotTileMin;                // samples that make a one-pixel tile hot
+constexpr int64_t kHotMin = policy::kHotTileMin;                // samples that make a one-pixel tile hot
 static_assert(kHotMin == 2 * kHotChunk, "hot tiles: at least two ranges");
 
 template <int POL, bool HALF>
@@ -1016,38 +1016,20 @@ void hot_release(cm2_tiles *t)
 int hot_plan(cm2_tiles *t, hipStream_t st)
 {
     hot_release(t);
-    std::vector<uint8_t> flag((size_t)t->ntiles, 0);
-    std::vector<int64_t> range, tiles;
-    std::vector<int> range_tile;                             // (fused form: which hot tile a range belongs to)
-    t->hot_chunk0.assign(1, 0);
-    for (int64_t b = 0; b < t->ntiles; ++b) {
-        const int64_t n = t->tile_count[(size_t)b];
-        if (t->tile_p0[(size_t)b + 1] - t->tile_p0[(size_t)b] != 1 || n < kHotMin) continue;
-        flag[(size_t)b] = 1;
-        const int64_t c0 = (int64_t)range.size() / 2;
-        // (ranges in time order: kHotChunk consecutive samples of the bucket each)
-        const int64_t a1 = t->tile_off[(size_t)b + 1];
-        for (int64_t k = t->tile_off[(size_t)b]; k < a1; k += kHotChunk) {
-            range.push_back(k);
-            range.push_back(k + kHotChunk < a1 ? k + kHotChunk : a1);
-        }
-        tiles.push_back(t->tile_p0[(size_t)b]);
-        tiles.push_back(c0);
-        tiles.push_back((int64_t)range.size() / 2 - c0);
-        range_tile.resize(range.size() / 2, (int)t->hot_tile.size());
-        t->hot_tile.push_back(b);
-        t->hot_chunk0.push_back((int64_t)range.size() / 2);
-    }
+    const policy::HotRanges h = policy::hot_ranges(t->tile_p0, t->tile_off, kHotChunk);
+    const std::vector<int64_t> &range = h.range, &tiles = h.tiles;
+    t->hot_tile = h.hot_tile;
+    t->hot_chunk0 = h.hot_chunk0;
     if (t->hot_tile.empty()) return 0;
-    CM2_HIP(cm2::dev_malloc(&t->d_hot_flag, flag.size()));
+    CM2_HIP(cm2::dev_malloc(&t->d_hot_flag, h.flag.size()));
     CM2_HIP(cm2::dev_malloc(&t->d_hot_range, sizeof(int64_t) * range.size()));
     CM2_HIP(cm2::dev_malloc(&t->d_hot_tiles, sizeof(int64_t) * tiles.size()));
     CM2_HIP(cm2::dev_malloc(&t->d_hot_partial, sizeof(double) * 3 * (range.size() / 2)));
-    CM2_HIP(cm2::upload(t->d_hot_flag, flag.data(), flag.size(), st));
+    CM2_HIP(cm2::upload(t->d_hot_flag, h.flag.data(), h.flag.size(), st));
     CM2_HIP(cm2::upload(t->d_hot_range, range.data(), sizeof(int64_t) * range.size(), st));
     CM2_HIP(cm2::upload(t->d_hot_tiles, tiles.data(), sizeof(int64_t) * tiles.size(), st));
-    CM2_HIP(cm2::dev_malloc(&t->d_hot_range_tile, sizeof(int) * range_tile.size()));
-    CM2_HIP(cm2::upload(t->d_hot_range_tile, range_tile.data(), sizeof(int) * range_tile.size(), st));
+    CM2_HIP(cm2::dev_malloc(&t->d_hot_range_tile, sizeof(int) * h.range_tile.size()));
+    CM2_HIP(cm2::upload(t->d_hot_range_tile, h.range_tile.data(), sizeof(int) * h.range_tile.size(), st));
     CM2_HIP(hipStreamSynchronize(st));
     return 0;
 }
@@ -1093,31 +1075,7 @@ void fx_release(cm2_tiles *t)
 // a tile that k_Pt_hot takes over (hot_plan): its slices do not count when the slice length is tuned
 static bool fx_hot_tile(const cm2_tiles *t, int64_t b)
 {
-    return t->tile_p0[(size_t)b + 1] - t->tile_p0[(size_t)b] == 1 && t->tile_count[(size_t)b] >= kHotMin;
-}
-
-// The slices of the plan for the slice length S, as (first address, end) pairs in the order the
-// kernel walks them: tile after tile, a tile's bucket cut into pieces of S with a shorter last one.
-// slice0[b] = first slice of tile b.
-static void fx_slices(const cm2_tiles *t, int S, std::vector<int64_t> &slice0, std::vector<int64_t> &pairs)
-{
-    slice0.assign((size_t)t->ntiles + 1, 0);
-    pairs.clear();
-    for (int64_t b = 0; b < t->ntiles; ++b) {
-        slice0[(size_t)b] = (int64_t)pairs.size() / 2;
-        const int64_t a1 = t->tile_off[(size_t)b + 1];
-        for (int64_t k = t->tile_off[(size_t)b]; k < a1; k += S) {
-            pairs.push_back(k);
-            pairs.push_back(k + S < a1 ? k + S : a1);
-        }
-    }
-    slice0[(size_t)t->ntiles] = (int64_t)pairs.size() / 2;
-}
-
-static bool fx_serial()
-{
-    const char *e = getenv("CM2_FX_BUILD");
-    return e && strcmp(e, "serial") == 0;
+    return policy::is_hot_tile(t->tile_p0[(size_t)b + 1] - t->tile_p0[(size_t)b], t->tile_count[(size_t)b]);
 }
 
 // groups per full slice of S samples and the fraction of slices with more groups than threads,
@@ -1127,8 +1085,9 @@ int fx_estimate(const cm2_tiles *t, int S, hipStream_t st, double *mean_groups, 
 {
     *mean_groups = 0.0;
     *over = 0.0;
-    std::vector<int64_t> pairs, slice0, all;
-    fx_slices(t, S, slice0, all);
+    std::vector<int64_t> pairs;
+    const policy::Slices sl_all = policy::slices(t->tile_off, S);
+    const std::vector<int64_t> &slice0 = sl_all.slice0, &all = sl_all.pairs;
     int64_t seen = 0;
     for (int64_t b = 0; b < t->ntiles; ++b) {
         if (fx_hot_tile(t, b)) continue;
@@ -1173,10 +1132,13 @@ int fx_estimate(const cm2_tiles *t, int S, hipStream_t st, double *mean_groups, 
 // *over = fraction of slices with more groups than threads
 int fx_build(cm2_tiles *t, int S, hipStream_t st, double *mean_groups, double *over)
 {
+    // (k_fx_build sorts a slice in LDS; fx_max_slice allows no longer one)
+    CM2_CHECK(S <= kFbMaxS, "cm2_tiles: a slice of %d samples is longer than the %d the list builder holds", S, kFbMaxS);
     fx_release(t);
     const int64_t nv = t->nvalid;
-    std::vector<int64_t> slice0, k0;                 // k0: (first address, end) of every slice
-    fx_slices(t, S, slice0, k0);
+    policy::Slices sl = policy::slices(t->tile_off, S);
+    const std::vector<int64_t> &slice0 = sl.slice0;
+    std::vector<int64_t> &k0 = sl.pairs;             // k0: (first address, end) of every slice
     const int64_t nslices = slice0[(size_t)t->ntiles];
     CM2_CHECK(nslices < ((int64_t)1 << 31), "cm2_tiles: too many slices");
     {
@@ -1203,11 +1165,14 @@ int fx_build(cm2_tiles *t, int S, hipStream_t st, double *mean_groups, double *o
         DevTemp<char> d_temp;
         CM2_HIP(d_k0.alloc(k0.size()));
         CM2_HIP(cm2::upload(d_k0, k0.data(), sizeof(int64_t) * k0.size(), st));
+        // one workgroup per slice (k_fx_build) unless CM2_FX_BUILD=serial asks for the radix sort and
+        // the one-thread-per-slice packer (k_fx_pack): other lists, the same sums
+        const bool serial = t->sw.fx_serial;
         // (k_fx_pack, the serial builder of the global order, reads the slices as a cut list: slice s =
         //  [cut[s], cut[s + 1]))
         DevTemp<int64_t> d_k0s;
         std::vector<int64_t> cuts;
-        if (fx_serial() || S > kFbMaxS) {
+        if (serial) {
             for (int64_t i = 0; i < nslices; ++i) cuts.push_back(k0[(size_t)(2 * i)]);
             cuts.push_back(nv);
             CM2_HIP(d_k0s.alloc(cuts.size()));
@@ -1219,9 +1184,6 @@ int fx_build(cm2_tiles *t, int S, hipStream_t st, double *mean_groups, double *o
         CM2_HIP(hipMemsetAsync(d_overflow.p, 0, sizeof(unsigned int), st));
         const uint32_t qmask = t->half ? 0x7FFFu : 0xFFFFu;
         const int pgrid = (int)((nslices + 63) / 64);
-        // one workgroup per slice (k_fx_build) unless CM2_FX_BUILD=serial asks for the radix sort and
-        // the one-thread-per-slice packer (k_fx_pack): other lists, the same sums
-        const bool serial = fx_serial() || S > kFbMaxS;
         if (serial) {
             CM2_HIP(keys_in.alloc(nv));
             CM2_HIP(keys_out.alloc(nv));
@@ -1337,112 +1299,22 @@ int fx_build(cm2_tiles *t, int S, hipStream_t st, double *mean_groups, double *o
 }
 
 // ------------------------------------------------------------------- parts ----------
-// Finish time of `items` (samples each, in dispatch order) over the ideal (total / slots).  `slots`
-// workgroups are resident and take the next item as one finishes; the kernel is bandwidth bound, so the
-// resident workgroups share the chip's rate equally -- but one workgroup alone cannot use more than
-// about 1.5 x its share of the full chip (measured at C4 size: a slice takes 3.7 us with 512 workgroups
-// resident, 2.5 us with 51), which is what makes a few items left over at the end expensive.
-static double parts_makespan(const std::vector<int64_t> &items, int slots)
-{
-    const double rmax = 1.5;
-    std::vector<double> heap;                               // min-heap: finish "virtual time" of the active items
-    auto cmp = [](double a, double b2) { return a > b2; };
-    double V = 0.0, T = 0.0, total = 0.0;                   // virtual time (work done per active item), real time
-    size_t next = 0;
-    auto rate = [&]() {
-        const double fair = (double)slots / (double)(heap.empty() ? 1 : heap.size());
-        return fair < rmax ? fair : rmax;
-    };
-    for (; next < items.size() && (int)heap.size() < slots; ++next) {
-        heap.push_back((double)items[next] + 4096.0);      // (+ zeroing and writing the tile copy)
-        std::push_heap(heap.begin(), heap.end(), cmp);
-    }
-    for (int64_t x : items) total += (double)x + 4096.0;
-    while (!heap.empty()) {
-        const double vf = heap.front();
-        T += (vf - V) / rate();
-        V = vf;
-        std::pop_heap(heap.begin(), heap.end(), cmp);
-        heap.pop_back();
-        if (next < items.size()) {
-            heap.push_back(V + (double)items[next++] + 4096.0);
-            std::push_heap(heap.begin(), heap.end(), cmp);
-        }
-    }
-    return total > 0.0 ? T * (double)slots / total : 1.0;
-}
-
-// Shares the slices of heavy tiles out to several workgroups (see cm2_tiles.h).  The part length is
-// chosen by simulation: a tile of more than 1.1 x target samples is cut into ceil(load / target) parts
-// of equal slice counts, for targets between 1.25 and 0.2 of the mean load per resident workgroup; the
-// target with the earliest simulated finish wins (fewer parts on a tie).  Parts are dispatched in tile
-// order, i.e. by ascending address: dispatched by descending load instead (which scatters the
-// workgroups' streams over the buffers) the same parts took 0.45 instead of 0.42 ms at C4 size
-// (profiles/r04_uneven_parts.md).  CM2_PT_PARTS=0 keeps one workgroup per tile, CM2_PT_PARTS=<samples>
-// fixes the target.
+// Shares the slices of heavy tiles out to several workgroups (see cm2_tiles.h): the part length and the
+// parts of every tile are policy::choose_parts' (CM2_PT_PARTS=0 keeps one workgroup per tile,
+// CM2_PT_PARTS=<samples> fixes the target); here they become the plan's part lists and scratch.
 int parts_plan(cm2_tiles *t, hipStream_t st)
 {
     if (!t->pt_split || t->fx_nslices == 0) return 0;
-    int forced = -1;
-    if (const char *e = getenv("CM2_PT_PARTS")) forced = atoi(e);
-    if (forced == 0) return 0;
-    std::vector<int64_t> slice0, k0;
-    fx_slices(t, t->fx_S, slice0, k0);
-    // The simulated machine is the MI355X this library is written for (kNumCU), NOT the live device: part
-    // boundaries change the order in which a pixel's terms are added, and the header promises that they
-    // depend on the plan only -- the same bits on any partition mode or device count.
-    // (two workgroups per CU when their LDS fits twice, fx_max_slice)
-    const int slots = (fx_lds_bytes(t, t->fx_S) <= 79 * 1024 ? 2 : 1) * kNumCU;
-    std::vector<int64_t> load((size_t)t->ntiles, 0);
-    int64_t total = 0;
+    const std::vector<int64_t> slice0 = policy::slices(t->tile_off, t->fx_S).slice0;
+    // (two workgroups per CU of the simulated machine when their LDS fits twice, fx_max_slice)
+    const int slots = (fx_lds_bytes(t, t->fx_S) <= 79 * 1024 ? 2 : 1) * policy::kSimCUs;
+    std::vector<int64_t> load((size_t)t->ntiles, 0), nslices((size_t)t->ntiles, 0);
     for (int64_t b = 0; b < t->ntiles; ++b) {
-        if (fx_hot_tile(t, b)) continue;
-        load[(size_t)b] = t->tile_count[(size_t)b];
-        total += load[(size_t)b];
+        nslices[(size_t)b] = slice0[(size_t)b + 1] - slice0[(size_t)b];
+        if (!fx_hot_tile(t, b)) load[(size_t)b] = t->tile_count[(size_t)b];
     }
-    if (total == 0) return 0;
-    auto parts_of = [&](int64_t b, int64_t target) -> int64_t {
-        const int64_t ns = slice0[(size_t)b + 1] - slice0[(size_t)b];
-        if (load[(size_t)b] * 10 <= target * 11 || ns <= 1) return 1;
-        int64_t k = (load[(size_t)b] + target - 1) / target;
-        return k < ns ? k : ns;
-    };
-    auto items_for = [&](int64_t target, std::vector<int64_t> &items) {
-        items.clear();
-        for (int64_t b = 0; b < t->ntiles; ++b) {
-            if (load[(size_t)b] == 0) continue;
-            const int64_t k = parts_of(b, target);
-            for (int64_t j = 0; j < k; ++j) items.push_back(load[(size_t)b] / k);
-        }
-    };
-    const double per_slot = (double)total / (double)slots;
-    int64_t best_target = 0;
-    double best = 1e30;
-    size_t best_items = 0;
-    std::vector<int64_t> items;
-    if (forced > 0) {
-        best_target = forced;
-        items_for(best_target, items);
-        best = parts_makespan(items, slots);
-    } else {
-        // one workgroup per tile is kept unless some split finishes at least 5 % earlier; among the
-        // splits the earliest finish, and the fewest parts within 1 % of it
-        items_for(INT64_MAX / 16, items);
-        const double whole = parts_makespan(items, slots);
-        for (int step = 0; step <= 42; ++step) {
-            const int64_t target = (int64_t)(per_slot * (1.25 - 0.025 * step)) + 1;
-            if (target < 4 * t->fx_S) break;                // (parts of a few slices only: not worth a copy)
-            items_for(target, items);
-            const double mk = parts_makespan(items, slots);
-            if (mk < best - 0.01 || (mk < best + 0.01 && items.size() < best_items)) {
-                best = mk;
-                best_target = target;
-                best_items = items.size();
-            }
-        }
-        if (best > 0.95 * whole) best_target = 0;
-    }
-    if (best_target == 0) return 0;
+    const policy::PartsChoice choice = policy::choose_parts(load, nslices, t->fx_S, slots, t->sw.pt_parts);
+    if (choice.target == 0) return 0;
     // the parts in tile order (= dispatch order), their scratch slots (split tiles only)
     std::vector<int4> parts;
     std::vector<int64_t> multi;
@@ -1450,8 +1322,7 @@ int parts_plan(cm2_tiles *t, hipStream_t st)
     int64_t slot = 0;
     for (int64_t b = 0; b < t->ntiles; ++b) {
         t->tile_part0[(size_t)b] = (int64_t)parts.size();
-        const int64_t s0 = slice0[(size_t)b], ns = slice0[(size_t)b + 1] - s0;
-        const int64_t k = load[(size_t)b] ? parts_of(b, best_target) : 1;
+        const int64_t s0 = slice0[(size_t)b], ns = nslices[(size_t)b], k = choice.parts[(size_t)b];
         if (k > 1) {
             t->multi_tile.push_back(b);
             multi.push_back(t->tile_p0[(size_t)b] * t->pol);
@@ -1460,7 +1331,7 @@ int parts_plan(cm2_tiles *t, hipStream_t st)
             multi.push_back(k);
         }
         for (int64_t j = 0; j < k; ++j) {
-            const int64_t a = s0 + ns * j / k, e = s0 + ns * (j + 1) / k;
+            const int64_t a = s0 + policy::part_slice(ns, j, k), e = s0 + policy::part_slice(ns, j + 1, k);
             parts.push_back(make_int4((int)b, (int)(e - a), (int)a, k > 1 ? (int)(slot + j) : -1));
         }
         if (k > 1) slot += k;
@@ -1472,7 +1343,7 @@ int parts_plan(cm2_tiles *t, hipStream_t st)
     }
     t->nparts = (int64_t)parts.size();
     t->part_slots = slot;
-    t->part_makespan = best;
+    t->part_makespan = choice.makespan;
     CM2_HIP(cm2::dev_malloc(&t->d_parts, sizeof(int4) * parts.size()));
     CM2_HIP(cm2::dev_malloc(&t->d_multi, sizeof(int64_t) * multi.size()));
     CM2_HIP(cm2::dev_malloc(&t->d_part_buf, sizeof(double) * (size_t)slot * (size_t)t->tp * (size_t)t->pol));
@@ -1487,8 +1358,7 @@ int parts_plan(cm2_tiles *t, hipStream_t st)
 // launch).  CM2_PT_FUSE=0 keeps the separate kernels.
 int fused_plan(cm2_tiles *t, hipStream_t st)
 {
-    if (const char *e = getenv("CM2_PT_FUSE"))
-        if (atoi(e) == 0) return 0;
+    if (!t->sw.pt_fuse) return 0;
     const size_t nhot = t->hot_tile.size();
     if (nhot == 0) return 0;
     t->fx_count_bytes = (sizeof(unsigned int) * nhot + 15) / 16 * 16;
@@ -1576,8 +1446,6 @@ namespace cm2 {
 
 void fx_free(cm2_tiles *t) { fx_release(t); }
 
-bool fx_serial_build() { return fx_serial(); }
-
 // longest slice the kernel can stage beside the tile: 4 values a thread at most, and short enough for
 // two workgroups per CU (<= 79 KB each) whenever some slice length allows that
 int fx_max_slice(const cm2_tiles *t)
@@ -1652,27 +1520,19 @@ static int fx_plan_build(const cm2_tiles *tc, hipStream_t st, bool *use)
             mark.ok = true;
             return 0;
         }
-        int forced = 0;
-        if (const char *e = getenv("CM2_PT_SLICE")) forced = atoi(e);
+        const int forced = t->sw.pt_slice;
         double mean = 0.0, over = 0.0;
         if (forced >= 64 && forced <= 4 * kFxT) {
             if (int rc = fx_build(t, forced < smax ? forced : smax, st, &mean, &over)) return rc;
         } else {
             int S = 1536 < smax ? 1536 : smax;
-            auto wanted = [&](int S_now) {
-                int want = (int)(0.92 * kFxT * S_now / mean) / 64 * 64;
-                if (over > 0.10) want = want < S_now * 7 / 8 ? want : S_now * 7 / 8 / 64 * 64;
-                if (want > smax) want = smax;
-                if (want < 256) want = 256;
-                return want;
-            };
-            if (!fx_serial() && S <= kFbMaxS) {           // first guess from a sample of the slices
+            if (!t->sw.fx_serial) {                       // first guess from a sample of the slices
                 if (int rc = fx_estimate(t, S, st, &mean, &over)) return rc;
-                if (mean > 0.0) S = wanted(S);
+                if (mean > 0.0) S = policy::wanted_slice(S, mean, over, smax, kFxT);
             }
             if (int rc = fx_build(t, S, st, &mean, &over)) return rc;
             for (int iter = 0; iter < 3 && mean > 0.0; ++iter) {
-                const int want = wanted(S);
+                const int want = policy::wanted_slice(S, mean, over, smax, kFxT);
                 const bool close_enough = want >= S * 15 / 16 && want <= S * 17 / 16 && over <= 0.10;
                 if (close_enough || want == S) break;
                 S = want;
