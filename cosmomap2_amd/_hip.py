@@ -17,6 +17,7 @@ _vp = ctypes.c_void_p
 _i64 = ctypes.c_int64
 _int = ctypes.c_int
 _dbl = ctypes.c_double
+_u64 = ctypes.c_uint64
 
 # name -> argtypes (restype is int unless listed in _RESTYPE)
 PROTOTYPES = {
@@ -108,6 +109,13 @@ PROTOTYPES = {
     "cm2_psd_info": [_vp, ctypes.POINTER(_i64)],
     "cm2_psd_welch": [_vp, _vp, ctypes.POINTER(_i64), _i64, _dbl, _vp, _vp],
     "cm2_noise_bands_from_psd": [_vp, _i64, _i64, _dbl, _i64, _vp, _vp],
+    "cm2_rng_fill": [_int, _u64, _u64, _u64, _i64, _i64, _vp, _vp],
+    "cm2_noise_filter_from_psd": [_vp, _i64, _i64, _dbl, _i64, _vp, _vp],
+    "cm2_noise_sim_create": [ctypes.POINTER(_vp), ctypes.POINTER(_dbl), _i64, ctypes.POINTER(_i64), _i64, _u64, _u64,
+                             _vp],
+    "cm2_noise_sim_destroy": [_vp],
+    "cm2_noise_sim_info": [_vp, ctypes.POINTER(_i64)],
+    "cm2_noise_sim_draw": [_vp, _u64, _dbl, _int, _vp, _vp],
 }
 _RESTYPE = {"cm2_last_error": ctypes.c_char_p, "cm2_reduce_work_doubles": _i64,
             "cm2_gemm_tn_work_doubles": _i64}
@@ -164,8 +172,8 @@ ERR_OUT_OF_MEMORY = 3          # CM2_ERR_OUT_OF_MEMORY of include/cosmomap2.h
 # Entry points that may be called again after an out-of-memory failure: they build a new object (a failed
 # build frees what it had made) or overwrite their outputs from their inputs.  NOT in the list: the in-place
 # updates (cm2_axpy, cm2_scal, cm2_Z_axpy, cm2_panel_gemm with accumulate, cm2_pcg_update_*,
-# cm2_flag_samples, cm2_compact_*), which a second run would apply twice, and the drivers with callbacks
-# (cm2_pcg, cm2_pcg_sharded, cm2_arnoldi).
+# cm2_flag_samples, cm2_compact_*, cm2_noise_sim_draw with add), which a second run would apply twice, and the
+# drivers with callbacks (cm2_pcg, cm2_pcg_sharded, cm2_arnoldi).
 RESTARTABLE = frozenset([
     "cm2_pointing_create", "cm2_pointing_build_sell", "cm2_pointing_set_weights",
     "cm2_P_apply", "cm2_Pt_apply", "cm2_PtNP_diag_apply",
@@ -180,6 +188,7 @@ RESTARTABLE = frozenset([
     "cm2_filter_create", "cm2_filter_apply", "cm2_filter_apply_tiles",
     "cm2_cutsky_to_fullsky", "cm2_fullsky_to_cutsky", "cm2_ground_bin_sums", "cm2_ground_subtract",
     "cm2_psd_create", "cm2_psd_welch", "cm2_noise_bands_from_psd",
+    "cm2_rng_fill", "cm2_noise_filter_from_psd", "cm2_noise_sim_create",
 ])
 
 

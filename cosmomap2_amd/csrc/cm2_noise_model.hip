@@ -12,6 +12,9 @@
 //                            G = 1/S, c_j = irfft(G, L)[j] as a fixed-order cosine sum, Bartlett taper
 //                            a_j = (1 - j/lambda) c_j.  The symbol of the band is G smoothed by the Fejer
 //                            kernel (>= 0), so every block is SPD by construction.
+//   cm2_noise_filter_from_psd the same with G = sqrt(S): the band g of the symmetric FIR filter that colours
+//                            white noise to the spectrum |g^|^2, g^ = sqrt(S) smoothed by the Fejer kernel
+//                            (cm2_noise_sim.hip applies it).
 //
 // The Welch path runs over batches of a FIXED number of segments (set at cm2_psd_create from nperseg and the
 // workspace cap; the last batch is padded with zero segments), so a segment's rocFFT transform is the same
@@ -131,6 +134,22 @@ __global__ __launch_bounds__(256) void k_bands_inverse(const double *__restrict_
     const double S = psd[b * nfreq + kk] * fs / m;
     if (!(S > 0.0) || !isfinite(S)) atomicMin(bad, (unsigned long long)(b * nfreq + kk));
     G[i] = 1.0 / S;
+}
+
+// G[b][k] = sqrt(S_k), same S.  Zero is allowed; the first (block, bin) whose S is negative or not finite
+// goes to *bad.
+__global__ __launch_bounds__(256) void k_bands_sqrt(const double *__restrict__ psd, int64_t nb, int64_t nfreq,
+                                                     double fs, double *__restrict__ G,
+                                                     unsigned long long *__restrict__ bad)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nb * nfreq) return;
+    const int64_t b = i / nfreq, k = i - b * nfreq;
+    const int64_t kk = k == 0 ? 1 : k;
+    const double m = (kk == nfreq - 1) ? 1.0 : 2.0;
+    const double S = psd[b * nfreq + kk] * fs / m;
+    if (!(S >= 0.0) || !isfinite(S)) atomicMin(bad, (unsigned long long)(b * nfreq + kk));
+    G[i] = sqrt(S);
 }
 
 // cos(2 pi m / L), m < L (2m/L is exact: L is a power of two)
@@ -305,17 +324,17 @@ extern "C" int cm2_psd_welch(cm2_psd *p, const double *d_tod, const int64_t *h_s
     return 0;
 }
 
-extern "C" int cm2_noise_bands_from_psd(const double *d_psd, int64_t nb, int64_t nperseg, double fsample,
-                                        int64_t lambda, double *d_bands, void *stream_)
+// PSD -> band with G = 1/S (sqrt_mode 0) or G = sqrt(S) (1): the two entry points below
+static int bands_from_psd(const char *who, int sqrt_mode, const double *d_psd, int64_t nb, int64_t nperseg,
+                          double fsample, int64_t lambda, double *d_bands, void *stream_)
 {
-    CM2_CHECK(d_psd && d_bands, "cm2_noise_bands_from_psd: NULL argument");
-    CM2_CHECK(nb >= 1, "cm2_noise_bands_from_psd: nb=%lld < 1", (long long)nb);
-    CM2_CHECK(pow2_in_range(nperseg), "cm2_noise_bands_from_psd: nperseg=%lld is not a power of two in [256, 65536]",
+    CM2_CHECK(d_psd && d_bands, "%s: NULL argument", who);
+    CM2_CHECK(nb >= 1, "%s: nb=%lld < 1", who, (long long)nb);
+    CM2_CHECK(pow2_in_range(nperseg), "%s: nperseg=%lld is not a power of two in [256, 65536]", who,
               (long long)nperseg);
-    CM2_CHECK(lambda >= 1 && lambda <= nperseg / 2, "cm2_noise_bands_from_psd: lambda=%lld outside [1, %lld]",
+    CM2_CHECK(lambda >= 1 && lambda <= nperseg / 2, "%s: lambda=%lld outside [1, %lld]", who,
               (long long)lambda, (long long)(nperseg / 2));
-    CM2_CHECK(fsample > 0.0 && std::isfinite(fsample), "cm2_noise_bands_from_psd: fsample=%g is not positive",
-              fsample);
+    CM2_CHECK(fsample > 0.0 && std::isfinite(fsample), "%s: fsample=%g is not positive", who, fsample);
     hipStream_t stream = as_stream(stream_);
     const int64_t L = nperseg, nfreq = L / 2 + 1;
     DevTemp<double> G, tab;
@@ -324,8 +343,11 @@ extern "C" int cm2_noise_bands_from_psd(const double *d_psd, int64_t nb, int64_t
     CM2_HIP(tab.alloc(L));
     CM2_HIP(bad.alloc(1));
     CM2_HIP(hipMemsetAsync(bad, 0xFF, sizeof(unsigned long long), stream));
-    k_bands_inverse<<<(unsigned)((nb * nfreq + kBlock - 1) / kBlock), kBlock, 0, stream>>>(d_psd, nb, nfreq, fsample,
-                                                                                           G, bad);
+    const unsigned grid = (unsigned)((nb * nfreq + kBlock - 1) / kBlock);
+    if (sqrt_mode)
+        k_bands_sqrt<<<grid, kBlock, 0, stream>>>(d_psd, nb, nfreq, fsample, G, bad);
+    else
+        k_bands_inverse<<<grid, kBlock, 0, stream>>>(d_psd, nb, nfreq, fsample, G, bad);
     CM2_LAUNCH_OK();
     unsigned long long h_bad = 0;
     CM2_HIP(cm2::read_back(&h_bad, bad, sizeof(h_bad), stream));
@@ -333,6 +355,9 @@ extern "C" int cm2_noise_bands_from_psd(const double *d_psd, int64_t nb, int64_t
         const long long b = (long long)(h_bad / (unsigned long long)nfreq), k = (long long)(h_bad % nfreq);
         double v = 0.0;
         CM2_HIP(cm2::read_back(&v, d_psd + h_bad, sizeof(v), stream));
+        if (sqrt_mode)
+            CM2_CHECK(false, "PSD of block %lld is negative or not finite at bin %lld (value %g): no colouring "
+                      "band can be built from it", b, k, v);
         CM2_CHECK(false, "PSD of block %lld is not positive and finite at bin %lld (value %g): no inverse-noise "
                   "band can be built from it", b, k, v);
     }
@@ -343,4 +368,16 @@ extern "C" int cm2_noise_bands_from_psd(const double *d_psd, int64_t nb, int64_t
     CM2_LAUNCH_OK();
     CM2_HIP(hipStreamSynchronize(stream));      // (G, tab go back to the cache on return)
     return 0;
+}
+
+extern "C" int cm2_noise_bands_from_psd(const double *d_psd, int64_t nb, int64_t nperseg, double fsample,
+                                        int64_t lambda, double *d_bands, void *stream_)
+{
+    return bands_from_psd("cm2_noise_bands_from_psd", 0, d_psd, nb, nperseg, fsample, lambda, d_bands, stream_);
+}
+
+extern "C" int cm2_noise_filter_from_psd(const double *d_psd, int64_t nb, int64_t nperseg, double fsample,
+                                         int64_t lambda, double *d_bands, void *stream_)
+{
+    return bands_from_psd("cm2_noise_filter_from_psd", 1, d_psd, nb, nperseg, fsample, lambda, d_bands, stream_);
 }

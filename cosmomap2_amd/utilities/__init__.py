@@ -6,3 +6,4 @@ from .process_ces import *                                   # noqa: F401,F403
 from .healpy_functions import *                              # noqa: F401,F403
 from .IOfiles import *                                       # noqa: F401,F403
 from .noise_model import *                                   # noqa: F401,F403
+from .noise_sim import *                                     # noqa: F401,F403

@@ -544,6 +544,48 @@ int cm2_psd_welch(cm2_psd *p, const double *d_tod, const int64_t *h_sizes, int64
 int cm2_noise_bands_from_psd(const double *d_psd, int64_t nb, int64_t nperseg, double fsample,
                              int64_t lambda, double *d_bands, void *stream);
 
+/* ---- n2: noise time streams drawn from a PSD --------------------------------------
+ * The reference has no simulator.  Everything is a function of (seed, realization, block, sample index)
+ * alone: grid sizes, call boundaries, the device and the way a TOD is sharded do not change a sample.
+ *
+ * cm2_rng_fill: d_out[0..n) = samples first .. first+n-1 (first, n >= 0) of the white stream
+ * (seed, realization, block): Philox4x64-10 with key [seed, realization]; output block j = 0, 1, ... (four
+ * uint64) is the Philox function of the counter [j + 1, block, 0, 0], i.e.
+ * numpy.random.Philox(key=[seed, realization], counter=[0, block, 0, 0]).random_raw() bit for bit.
+ *   kind 0  uniform in [0, 1): u = (raw >> 11) 2^-53, bit-equal to numpy.random.Generator(...).random()
+ *   kind 1  standard normal: Box-Muller over the pairs (u0, u1) and (u2, u3) of a counter block, samples
+ *           4j, 4j+1 from the first and 4j+2, 4j+3 from the second: r = sqrt(-2 log(1 - u_a)),
+ *           z_a = r cospi(2 u_b), z_b = r sinpi(2 u_b)  (1 - u_a is in (0, 1]: the logarithm never sees 0).
+ * Counter blocks cut by `first` or `first + n` are generated whole and masked.  Does not synchronise. */
+int cm2_rng_fill(int kind, uint64_t seed, uint64_t realization, uint64_t block, int64_t first, int64_t n,
+                 double *d_out, void *stream);
+/* The colouring band: cm2_noise_bands_from_psd with G = sqrt(S) in place of 1/S, g_j = (1 - j/lambda)
+ * irfft(sqrt(S), L)[j].  The symbol g^(w) = g_0 + 2 sum_j g_j cos(w j) is sqrt(S) smoothed by the Fejer kernel
+ * (>= 0), and white noise filtered with g has the spectrum |g^|^2 (S itself up to that resolution).  S = 0 is
+ * allowed; a bin with S < 0 or not finite fails with CM2_ERR_ARGUMENT naming the block and the bin. */
+int cm2_noise_filter_from_psd(const double *d_psd, int64_t nb, int64_t nperseg, double fsample,
+                              int64_t lambda, double *d_bands, void *stream);
+/* cm2_noise_sim: coloured noise for nblocks blocks of h_sizes[b] samples with the bands h_bands[b][0..lambda-1]
+ * (host).  Block b of a draw is
+ *     y_i = sum_{|j| < lambda} g_|j| w_{i + (lambda-1) + j},   i = 0 .. n_b - 1,
+ * with w the first n_b + 2 (lambda-1) normals (cm2_rng_fill, kind 1) of the stream (seed, realization,
+ * first_block + b): the valid part of the convolution, so every sample of the block has the autocovariance
+ * g * g, up to the block edges.  Blocks are independent streams: a handle for blocks [k0, k1) of a TOD, made
+ * with first_block = k0, draws the samples a handle for the whole TOD draws for those blocks.
+ * The handle owns two buffers of sum_b (n_b + 2 (lambda-1)) doubles and a cm2_noise Toeplitz operator
+ * (CM2_TOEPLITZ_AUTO) on the padded blocks, whose interior rows are the sum above.
+ * cm2_noise_sim_draw: d_out[0..nt) = (add ? d_out : 0) + scale * y.  No allocation, no host copy, does not
+ * synchronise; one handle must not run two draws at once.
+ * cm2_noise_sim_info: h_info[7] = nt, nblocks, lambda, padded samples, CM2_TOEPLITZ_* method of the
+ * operator, its FFT length (0: direct sum), bytes of the two padded buffers. */
+typedef struct cm2_noise_sim cm2_noise_sim;
+int cm2_noise_sim_create(cm2_noise_sim **out, const double *h_bands, int64_t lambda, const int64_t *h_sizes,
+                         int64_t nblocks, uint64_t seed, uint64_t first_block, void *stream);
+int cm2_noise_sim_destroy(cm2_noise_sim *s);
+int cm2_noise_sim_info(const cm2_noise_sim *s, int64_t *h_info);
+int cm2_noise_sim_draw(cm2_noise_sim *s, uint64_t realization, double scale, int add, double *d_out,
+                       void *stream);
+
 #ifdef __cplusplus
 }
 #endif
