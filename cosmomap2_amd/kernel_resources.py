@@ -28,8 +28,8 @@ NO_SPILL = [r"\bk_os_real<", r"\bk_P_tiles", r"\bk_Pt_tiles", r"\bk_Pt_hot", r"\
 
 # kernels that must not spill SGPRs to VGPR lanes either: the overlap-save instantiations the default dispatch
 # reaches below 4 GB of TOD (at 246-254 of 256 VGPRs a lane register spent on spilled scalars is one too many);
-# the flat-addressing forms of the plain and run-coded lists (<32, 1, false>, <32, 2, false>) keep 44 / 56
-NO_SGPR_SPILL = [r"\bk_os_real<32, 0, false>", r"\bk_os_real<32, [123], true>", r"\bk_os_real<32, 3, false>"]
+# the flat-addressing forms of the plain and run-coded lists (<1, false>, <2, false>) keep 44 / 56
+NO_SGPR_SPILL = [r"\bk_os_real<0, false>", r"\bk_os_real<[123], true>", r"\bk_os_real<3, false>"]
 
 _FIELDS = {"VGPRs": "vgpr", "AGPRs": "agpr", "SGPRs": "sgpr", "ScratchSize [bytes/lane]": "scratch_bytes_per_lane",
            "Occupancy [waves/SIMD]": "occupancy", "SGPRs Spill": "sgpr_spill", "VGPRs Spill": "vgpr_spill",
@@ -59,7 +59,7 @@ def demangle(names):
 
 
 def short(name):
-    """`(anonymous namespace)::k_os_real<32, 2, true>(args...)` -> `k_os_real<32, 2, true>`"""
+    """`(anonymous namespace)::k_os_real<2, true>(args...)` -> `k_os_real<2, true>`"""
     name = name.replace("(anonymous namespace)::", "").replace("void ", "")
     depth, cut = 0, len(name)
     for i, c in enumerate(name):
