@@ -1,12 +1,14 @@
 // cm2_plan_policy.h -- the host decisions of the tile plan and of its fixed-order P^T lists: where the pixel tiles
-// are cut, how a bucket is cut into slices, work items and hot ranges, and how the slices of heavy tiles are shared
-// out to workgroups.  Plain C++17 on host vectors: no device, no plan object, no environment, no hidden state -- a
+// are cut, how a bucket is cut into slices, work items and hot ranges, how the slices of heavy tiles are shared
+// out to workgroups, and for the fixed-order lists the LDS budget, the list offsets from the per-slice counts and the
+// tuning of the slice length.  Plain C++17 on host vectors: no device, no plan object, no environment, no hidden state -- a
 // rule can be changed here and its plan looked at on a CPU (tests/test_plan_policy_cpu.py).  Tile cuts and part
 // boundaries fix the order in which a pixel's terms are added, hence the bits: integer types, floating-point
-// expressions and tie rules are part of the result.  cm2_tiles.hip and cm2_tiles_fixed.hip turn these answers into
-// device data.
+// expressions and tie rules are part of the result.  cm2_tiles.hip, cm2_tiles_fixed.hip and cm2_fx_lists.hip turn
+// these answers into device data.
 #pragma once
 #include <algorithm>
+#include <cstddef>
 #include <cstdint>
 #include <vector>
 
@@ -184,6 +186,134 @@ inline int wanted_slice(int S, double mean_groups, double over, int smax, int th
     if (want > smax) want = smax;
     if (want < 256) want = 256;
     return want;
+}
+
+// The tuning of the slice length.  A rebuild is not worth it when the wanted length is within 1/16 of the built one
+// and few slices overflow, or when nothing would change.
+inline bool slice_settled(int S, int want, double over)
+{
+    const bool close_enough = want >= S * 15 / 16 && want <= S * 17 / 16 && over <= 0.10;
+    return close_enough || want == S;
+}
+constexpr int kSliceFirst = 1536;        // slice length of the first count
+constexpr int kSliceRebuilds = 3;        // rebuilds after the first build, at most
+// The slice lengths a plan tries, in order, the last one being the plan's.  build(S, mean, over) builds the lists for
+// S and answers the groups per full slice and the fraction of slices with more groups than threads; count(S, mean,
+// over) answers the same from a sample of the slices without building (sample_first = false: not asked, the serial
+// builders).  Both return non-zero on failure, which ends the tuning with that code.  forced (CM2_PT_SLICE) in [64,
+// 4 x threads] fixes the length, clamped to smax.  *S_out: the last length built.
+template <typename Count, typename Build>
+inline int tune_slice(int forced, int smax, int threads, bool sample_first, Count count, Build build, int *S_out)
+{
+    double mean = 0.0, over = 0.0;
+    int &S = *S_out;
+    if (forced >= 64 && forced <= 4 * threads) return build(S = forced < smax ? forced : smax, mean, over);
+    S = kSliceFirst < smax ? kSliceFirst : smax;
+    if (sample_first) {                                     // first guess from a sample of the slices
+        if (int rc = count(S, mean, over)) return rc;
+        if (mean > 0.0) S = wanted_slice(S, mean, over, smax, threads);
+    }
+    if (int rc = build(S, mean, over)) return rc;
+    for (int iter = 0; iter < kSliceRebuilds && mean > 0.0; ++iter) {
+        const int want = wanted_slice(S, mean, over, smax, threads);
+        if (slice_settled(S, want, over)) break;
+        S = want;
+        if (int rc = build(S, mean, over)) return rc;
+    }
+    return 0;
+}
+
+// ------------------------------------------------------- fixed-order lists: LDS, offsets -------
+constexpr int kFxThreads = 512;          // threads of k_Pt_tiles_fixed = groups of a slice handled in one round
+constexpr int kFxChunkSums = 128;        // chunk sums of hot runs a slice may hold, x 3 doubles
+// A CU has 160 KB of LDS.  What a workgroup may ask for so that
+constexpr size_t kLdsTwoPerCU = 79 * 1024;     // ... two workgroups are resident on a CU,
+constexpr size_t kLdsOnePerCU = 159 * 1024;    // ... one is.
+// LDS of k_Pt_tiles_fixed for slices of S samples: the tile's accumulators, two buffers of the slice's values (at
+// least two values a thread) and the chunk sums
+inline size_t fx_lds_bytes(int tp, int pol, int S)
+{
+    int vpt = (S + kFxThreads - 1) / kFxThreads;
+    vpt = vpt <= 2 ? 2 : vpt;
+    return sizeof(double) * ((size_t)tp * pol + 2 * (size_t)vpt * kFxThreads + 3 * (size_t)kFxChunkSums);
+}
+// longest slice the kernel can stage beside the tile: 4 values a thread at most, and short enough for
+// two workgroups per CU whenever some slice length allows that
+inline int fx_max_slice(int tp, int pol)
+{
+    int smax = 4 * kFxThreads;
+    {
+        int s2 = smax;
+        while (s2 > 2 * kFxThreads && fx_lds_bytes(tp, pol, s2) > kLdsTwoPerCU) s2 -= kFxThreads;
+        if (fx_lds_bytes(tp, pol, s2) <= kLdsTwoPerCU) smax = s2;
+    }
+    while (smax > 256 && fx_lds_bytes(tp, pol, smax) > kLdsOnePerCU) smax -= 256;
+    return smax;
+}
+// not even the shortest slice fits beside the tile: the plan uses the atomic P^T
+inline bool fx_tile_fills_lds(int tp, int pol) { return fx_lds_bytes(tp, pol, fx_max_slice(tp, pol)) > kLdsOnePerCU; }
+// workgroups of k_Pt_tiles_fixed a CU holds at the slice length S
+inline int fx_workgroups_per_cu(int tp, int pol, int S) { return fx_lds_bytes(tp, pol, S) <= kLdsTwoPerCU ? 2 : 1; }
+
+// Where every slice's lists begin, from the builders' counting pass.  counts[4 s + {0, 1, 2, 3}] = groups, tail runs,
+// tail entries and highest level of slice s (the slices of policy::slices, `sl`).  meta[2 s] = first group, meta[2 s
+// + 1] = first tail run | highest level << level_shift, tent_off[s] = first tail entry; entry [nslices] closes the
+// lists with the totals.  fits = the offsets hold them: groups and tail entries in 32 bits, tail runs below the level
+// field.  mean_groups: groups per full slice (S samples); over: fraction of slices with more groups than `threads`;
+// both over the tiles that are not `hot` ([ntiles], 1 = left to the hot-tile path).
+struct FxOffsets {
+    std::vector<uint32_t> meta, tent_off;
+    int64_t ngroups = 0, ntrun = 0, ntent = 0;
+    bool fits = false;
+    double mean_groups = 0.0, over = 0.0;
+};
+inline FxOffsets fx_offsets(const std::vector<uint32_t> &counts, const Slices &sl, const std::vector<uint8_t> &hot,
+                            int64_t S, int threads, int level_shift)
+{
+    const int64_t ntiles = (int64_t)sl.slice0.size() - 1, nslices = sl.slice0[(size_t)ntiles];
+    FxOffsets r;
+    r.meta.assign(2 * ((size_t)nslices + 1), 0);
+    r.tent_off.assign((size_t)nslices + 1, 0);
+    for (int64_t s = 0; s < nslices; ++s) {
+        r.meta[(size_t)(2 * s)] = (uint32_t)r.ngroups;
+        r.meta[(size_t)(2 * s + 1)] = (uint32_t)r.ntrun | (counts[(size_t)(4 * s + 3)] << level_shift);
+        r.tent_off[(size_t)s] = (uint32_t)r.ntent;
+        r.ngroups += counts[(size_t)(4 * s)];
+        r.ntrun += counts[(size_t)(4 * s + 1)];
+        r.ntent += counts[(size_t)(4 * s + 2)];
+    }
+    int64_t nfull = 0, nover = 0, ncounted = 0;
+    double gsum = 0.0;
+    for (int64_t b = 0; b < ntiles; ++b) {
+        if (hot[(size_t)b]) continue;
+        for (int64_t s = sl.slice0[(size_t)b]; s < sl.slice0[(size_t)b + 1]; ++s) {
+            ++ncounted;
+            if (counts[(size_t)(4 * s)] > (uint32_t)threads) ++nover;
+            if (sl.pairs[(size_t)(2 * s + 1)] - sl.pairs[(size_t)(2 * s)] == S) {
+                ++nfull;
+                gsum += counts[(size_t)(4 * s)];
+            }
+        }
+    }
+    r.meta[(size_t)(2 * nslices)] = (uint32_t)r.ngroups;
+    r.meta[(size_t)(2 * nslices + 1)] = (uint32_t)r.ntrun;
+    r.tent_off[(size_t)nslices] = (uint32_t)r.ntent;
+    r.fits = r.ngroups < ((int64_t)1 << 32) && r.ntent < ((int64_t)1 << 32) && r.ntrun < ((int64_t)1 << level_shift);
+    r.mean_groups = nfull ? gsum / (double)nfull : 0.0;
+    r.over = ncounted ? (double)nover / (double)ncounted : 0.0;
+    return r;
+}
+
+// the index range [lo, hi) of the entries of the ascending tile list `asc` that lie in [tile_lo, tile_hi)
+struct IndexRange {
+    int64_t lo, hi;
+};
+inline IndexRange tiles_in_range(const std::vector<int64_t> &asc, int64_t tile_lo, int64_t tile_hi)
+{
+    IndexRange r{0, (int64_t)asc.size()};
+    while (r.lo < r.hi && asc[(size_t)r.lo] < tile_lo) ++r.lo;
+    while (r.hi > r.lo && asc[(size_t)r.hi - 1] >= tile_hi) --r.hi;
+    return r;
 }
 
 // a tile that k_Pt_hot takes over: ONE pixel with at least kHotTileMin samples

@@ -1,5 +1,5 @@
 // cm2_tiles.h -- the tile-bucketed pointing plan shared by cm2_tiles.hip (plan, P, atomic P^T,
-// permutations) and cm2_tiles_fixed.hip (fixed-order P^T)
+// permutations), cm2_tiles_fixed.hip (fixed-order P^T) and cm2_fx_lists.hip (its list builders)
 #pragma once
 #include "cm2_pixindex.h"
 #include "cm2_plan_policy.h"
@@ -20,6 +20,94 @@ struct PlanSwitches {
     int pt_slice = 0;            // CM2_PT_SLICE=<samples in [64, 2048]>: fixes the slice length (0: tuned)
     int pt_parts = -1;           // CM2_PT_PARTS: 0 = one workgroup per tile, <samples> fixes the part length (-1: chosen)
     bool pt_fuse = true;         // CM2_PT_FUSE=0 (or no number): hot ranges and part copies in kernels of their own
+};
+
+// frees the device buffers it is given and clears the pointers
+template <typename... P>
+inline void dev_release(P *&...p) { ((p ? (void)dev_free(p) : (void)0, p = nullptr), ...); }
+struct NoCopy {
+    NoCopy() = default;
+    NoCopy(const NoCopy &) = delete;
+    NoCopy &operator=(const NoCopy &) = delete;
+};
+
+// The state of the fixed-order P^T in three parts, each the owner of its device buffers: reset() (and the
+// destructor) frees them, so that no table of pointers has to be kept in step with the fields.
+
+// fixed-order P^T (cm2_tiles_fixed.hip), built on first use: every tile bucket is cut into
+// slices of S consecutive TB samples; per slice the samples sorted by (pixel, time) are
+// packed into groups of 4 list entries that hold whole runs (= samples of one pixel).  The formats of the
+// entry word and of meta: cm2_fx_lists.h.
+struct FxLists : NoCopy {
+    int S = 0;
+    int64_t *d_slice0 = nullptr;     // [ntiles+1] first slice of every tile
+    uint2 *d_sk = nullptr;           // [nslices+1] {first TB position, samples} of every slice
+    uint2 *d_meta = nullptr;         // [nslices+1] {first group, first tail run | max level << 28}
+    uint4 *d_gent = nullptr;         // [ngroups] 4 entries: pl word | offset in slice << 16 | level << 28
+    double *d_ga = nullptr, *d_gb = nullptr;   // [4 ngroups] half angle (or cos, sin)
+    uint2 *d_trun = nullptr;         // [ntail runs + 1] {first tail entry, pixel in tile}
+    uint32_t *d_tent = nullptr;      // [ntail entries] entries of the runs kept out of the groups
+    double *d_ta = nullptr, *d_tb = nullptr;
+    int64_t ngroups = 0, nslices = 0;
+    ~FxLists() { reset(); }
+    void reset()
+    {
+        dev_release(d_slice0, d_sk, d_meta, d_gent, d_ga, d_gb, d_trun, d_tent, d_ta, d_tb);
+        S = 0;
+        ngroups = nslices = 0;
+    }
+};
+
+// PARTS of the fixed-order P^T (round 4, cm2_tiles_fixed.hip): on a hit map that is far from
+// uniform the tiles keep their width (only a pixel heavy enough for the hot-tile path becomes a
+// tile of its own) and the SLICES of a heavy tile are shared out to several workgroups, each
+// summing its consecutive slices in time order into its own copy of the tile; k_parts_combine adds
+// the copies in time order.  Part boundaries depend on the plan only: reproducible bit for bit;
+// a regrouped sum, ~1e-16 relative away from the serial one.  cm2_tiles::pt_split = the plan may do this
+// (set at create: unbalanced hit map, neither the equal-load cut nor the exact order asked for).
+struct FxParts : NoCopy {
+    std::vector<int64_t> tile_part0;    // [ntiles+1] first part of every tile (empty: no parts)
+    std::vector<int64_t> multi_tile;    // tiles with more than one part, ascending
+    int4 *d_parts = nullptr;            // [nparts] {tile, slices, first slice, scratch slot or -1}
+    int64_t *d_multi = nullptr;         // [nmulti][4] offset in the map, values, first scratch slot, parts
+    double *d_buf = nullptr;            // [scratch slots][tp * pol]
+    int64_t nparts = 0, slots = 0;
+    double makespan = 0.0;              // simulated finish time / ideal, 2 workgroups per CU
+    ~FxParts() { reset(); }
+    void reset()
+    {
+        dev_release(d_parts, d_multi, d_buf);
+        tile_part0.clear();
+        multi_tile.clear();
+        nparts = slots = 0;
+        makespan = 0.0;
+    }
+};
+
+// hot tiles of the fixed-order P^T: a tile that is ONE pixel with very many samples (a stare at
+// a source; the balanced tiling makes such a pixel a tile of its own) is reduced by many
+// workgroups, each summing a fixed range of kHotChunk consecutive samples of the bucket, and
+// the range sums are added in time order (cm2_tiles_fixed.hip)
+struct FxHot : NoCopy {
+    std::vector<int64_t> tile, chunk0;       // tile index, first chunk of every hot tile (+ total)
+    uint8_t *d_flag = nullptr;               // [ntiles]
+    int64_t *d_range = nullptr;              // [chunks][2] first / one-past-last TB position
+    int64_t *d_tiles = nullptr;              // [nhot][3] first pixel, first chunk, chunk count
+    double *d_partial = nullptr;             // [chunks][3]
+    // FUSED form (round 5): the ranges of a hot tile are work items at the end of the main launch and their
+    // sums are added up by the last range to finish (cm2_tiles_fixed.hip, FxFused)
+    void *d_fused = nullptr;                 // FxFused (device copy)
+    int *d_range_tile = nullptr;             // [chunks] index of the range's tile in d_tiles
+    unsigned int *d_count = nullptr;         // [nhot] arrival counters, zeroed before every launch
+    size_t count_bytes = 0;
+    ~FxHot() { reset(); }
+    void reset()
+    {
+        dev_release(d_flag, d_range, d_tiles, d_partial, d_fused, d_range_tile, d_count);
+        tile.clear();
+        chunk0.clear();
+        count_bytes = 0;
+    }
 };
 }  // namespace cm2
 
@@ -59,52 +147,14 @@ struct cm2_tiles {
     // identity of this plan for the caches other objects key on it (noise / filter lists): a
     // device address can be reused by a later plan, a plan id cannot
     uint64_t plan_id = 0;
-    // fixed-order P^T (cm2_tiles_fixed.hip), built on first use: every tile bucket is cut into
-    // slices of fx_S consecutive TB samples; per slice the samples sorted by (pixel, time) are
-    // packed into groups of 4 list entries that hold whole runs (= samples of one pixel)
+    // fixed-order P^T (cm2_tiles_fixed.hip), built on first use: lists, hot tiles and parts below
     int pt_fixed = 1;
-    int fx_S = 0;
     int fx_failed = 0;       // a build of the fixed-order lists failed: not retried on every apply
     std::vector<int64_t> tile_count;    // [ntiles] valid samples of every tile (host)
-    int64_t *d_fx_slice0 = nullptr;     // [ntiles+1] first slice of every tile
-    uint2 *d_fx_sk = nullptr;           // [nslices+1] {first TB position, samples} of every slice
-    uint2 *d_fx_meta = nullptr;         // [nslices+1] {first group, first tail run | max level << 28}
-    uint4 *d_fx_gent = nullptr;         // [ngroups] 4 entries: pl word | offset in slice << 16 | level << 28
-    double *d_fx_ga = nullptr, *d_fx_gb = nullptr;   // [4 ngroups] half angle (or cos, sin)
-    uint2 *d_fx_trun = nullptr;         // [ntail runs + 1] {first tail entry, pixel in tile}
-    uint32_t *d_fx_tent = nullptr;      // [ntail entries] entries of the runs kept out of the groups
-    double *d_fx_ta = nullptr, *d_fx_tb = nullptr;
-    int64_t fx_ngroups = 0, fx_nslices = 0;
-    // hot tiles of the fixed-order P^T: a tile that is ONE pixel with very many samples (a stare at
-    // a source; the balanced tiling makes such a pixel a tile of its own) is reduced by many
-    // workgroups, each summing a fixed range of kHotChunk consecutive samples of the bucket, and
-    // the range sums are added in time order (cm2_tiles_fixed.hip)
-    // PARTS of the fixed-order P^T (round 4, cm2_tiles_fixed.hip): on a hit map that is far from
-    // uniform the tiles keep their width (only a pixel heavy enough for the hot-tile path becomes a
-    // tile of its own) and the SLICES of a heavy tile are shared out to several workgroups, each
-    // summing its consecutive slices in time order into its own copy of the tile; k_parts_combine adds
-    // the copies in time order.  Part boundaries depend on the plan only: reproducible bit for bit;
-    // a regrouped sum, ~1e-16 relative away from the serial one.  pt_split = the plan may do this
-    // (set at create: unbalanced hit map, neither the equal-load cut nor the exact order asked for).
-    bool pt_split = false;
-    std::vector<int64_t> tile_part0;    // [ntiles+1] first part of every tile (empty: no parts)
-    std::vector<int64_t> multi_tile;    // tiles with more than one part, ascending
-    int4 *d_parts = nullptr;            // [nparts] {tile, slices, first slice, scratch slot or -1}
-    int64_t *d_multi = nullptr;         // [nmulti][4] offset in the map, values, first scratch slot, parts
-    double *d_part_buf = nullptr;       // [scratch slots][tp * pol]
-    int64_t nparts = 0, part_slots = 0;
-    double part_makespan = 0.0;         // simulated finish time / ideal, 2 workgroups per CU
-    std::vector<int64_t> hot_tile, hot_chunk0;   // tile index, first chunk of every hot tile (+ total)
-    uint8_t *d_hot_flag = nullptr;               // [ntiles]
-    int64_t *d_hot_range = nullptr;              // [chunks][2] first / one-past-last TB position
-    int64_t *d_hot_tiles = nullptr;              // [nhot][3] first pixel, first chunk, chunk count
-    double *d_hot_partial = nullptr;             // [chunks][3]
-    // FUSED form (round 5): the ranges of a hot tile are work items at the end of the main launch and their
-    // sums are added up by the last range to finish (cm2_tiles_fixed.hip, FxFused)
-    void *d_fx_fused = nullptr;                  // FxFused (device copy)
-    int *d_hot_range_tile = nullptr;             // [chunks] index of the range's tile in d_hot_tiles
-    unsigned int *d_fx_count = nullptr;          // [nhot] arrival counters, zeroed before every launch
-    size_t fx_count_bytes = 0;
+    bool pt_split = false;   // the plan may share a heavy tile's slices out to parts (FxParts)
+    cm2::FxLists fx;
+    cm2::FxParts parts;
+    cm2::FxHot hot;
 };
 
 namespace cm2 {
@@ -114,6 +164,5 @@ int fx_launch(const cm2_tiles *t, const double *d_tod_tb, double *d_out, int64_t
 void fx_free(cm2_tiles *t);
 int64_t fx_designed_bytes(const cm2_tiles *t);
 int fx_parts_info(const cm2_tiles *t, int64_t *h_info);   // cm2_tiles_pt_parts
-int fx_max_slice(const cm2_tiles *t);      // longest slice (samples) the fixed-order kernel's LDS budget allows
 }  // namespace cm2
 

@@ -897,7 +897,7 @@ extern "C" int cm2_tiles_info(const cm2_tiles *t, int64_t *h_info)
     h_info[0] = t->nt; h_info[1] = t->nvalid; h_info[2] = t->tp;
     h_info[3] = t->ntiles; h_info[4] = t->nitems; h_info[5] = t->half ? 1 : 0;
     h_info[6] = t->pt_fixed; h_info[7] = (int64_t)t->plan_id;
-    h_info[8] = t->fx_S; h_info[9] = cm2::fx_designed_bytes(t);
+    h_info[8] = t->fx.S; h_info[9] = cm2::fx_designed_bytes(t);
     // (the two fields of the span order removed in round 5: one span of all the chunks of kSplitChunk samples)
     h_info[10] = 1; h_info[11] = (t->nt + kSplitChunk - 1) / kSplitChunk * kSplitChunk;
     return 0;

@@ -37,22 +37,20 @@
 //     compiler waits with s_waitcnt vmcnt(N > 0) for the oldest slice only;
 //   * LDS adds instead of a load / add / store chain per run (12 of 24 LDS operations less per
 //     thread and slice, and no dependent round trip).
-#include "cm2_tiles.h"
+#include "cm2_fx_lists.h"
 
 #include <algorithm>
 #include <cstring>
 #include <mutex>
 
-#include <hipcub/hipcub.hpp>
-
 using namespace cm2;
 
 namespace {
 
-constexpr int kFxT = 512;               // threads = groups per slice handled in one round
+// (kFxT threads, the entry word, meta and the null entry: cm2_fx_lists.h, shared with the list builders.  The fields
+// are taken apart with its shifts and masks in place: as accessor functions they cost every instance of
+// k_Pt_tiles_fixed two more v_cndmask.)
 constexpr int kFxDepth = 2;             // slices fetched ahead of the one being reduced
-constexpr uint32_t kFxNull = 0xFFFFFFFFu;
-constexpr int kFxMaxLevel = 14;         // pieces of 4: runs up to 60 samples go into groups
 // Hot pixels.  A run longer than `chunk_min` entries inside one slice (a pixel that takes a large
 // share of a tile's samples: a stare at a source, a tile that is one pixel) is not walked term by
 // term by one thread -- 1536 dependent additions per slice while 511 threads wait -- but cut into
@@ -64,7 +62,7 @@ constexpr int kFxMaxLevel = 14;         // pieces of 4: runs up to 60 samples go
 // / CM2_PT_ORDER=exact keep the pure time order for every run.
 constexpr int kFxChunk = 32;
 constexpr int kFxChunkMinDefault = 256;
-constexpr int kFxMaxChunks = 128;       // per slice: S / kFxChunk + long runs <= 64 + 8
+constexpr int kFxMaxChunks = policy::kFxChunkSums;    // (128) per slice: S / kFxChunk + long runs <= 64 + 8
 
 // ------------------------------------------------------------------- fused form -----
 // The ranges of the hot tiles (a one-pixel tile of very many samples is reduced by ranges of kHotChunk samples)
@@ -123,6 +121,8 @@ __device__ __forceinline__ bool fx_last_arriver(unsigned int *counter, unsigned 
 // threads doing the work of k_Pt_hot's 1024: thread t is the virtual threads t and t + 512, each adding the
 // terms at positions vt, vt + 1024, ... of the range in that order; the 1024 sums are combined by the same
 // halving tree.  Then the last range of the tile adds the tile's range sums in time order (k_hot_combine).
+// (The term, the tree and the tail are written out here and in k_Pt_hot / k_hot_combine: each was tried as a shared
+// __forceinline__ helper and changed the instruction stream of some instance, profiles/fx_split_ab.md.)
 template <int POL, bool HALF>
 __device__ __forceinline__ void fx_hot_item(const FxFused &z, int64_t c, const double *__restrict__ v_tb,
                                             double *__restrict__ out, double *sm, int tid)
@@ -233,7 +233,7 @@ __global__ __launch_bounds__(kFxT, 4) void k_Pt_tiles_fixed(
 {
     constexpr int D = kFxDepth;
     constexpr bool ANG = POL > 1, TWO = POL > 1 && !HALF;
-    constexpr uint32_t QM = HALF ? 0x7FFFu : 0xFFFFu;
+    constexpr uint32_t QM = fx_pixel_mask(HALF);
     extern __shared__ double sm[];
     double *tile = sm;                                   // tp * POL accumulators
     // the slice's TOD values, TB order, in one of TWO buffers (slice j in buffer j & 1): a wave that
@@ -378,8 +378,8 @@ __global__ __launch_bounds__(kFxT, 4) void k_Pt_tiles_fixed(
             }
             __syncthreads();
             fetch(dd, j + D);
-            const uint32_t G = m1.x - m0.x, ntail = (m1.y & 0x0FFFFFFFu) - (m0.y & 0x0FFFFFFFu);
-            const int maxlevel = (int)(m0.y >> 28);      // highest level in this slice (plan time)
+            const uint32_t G = m1.x - m0.x, ntail = (m1.y & kFxRunMask) - (m0.y & kFxRunMask);
+            const int maxlevel = (int)(m0.y >> kFxLevelShift);     // highest level in this slice (plan time)
             for (uint32_t g0 = 0; g0 < G || g0 == 0; g0 += kFxT) {
                 const bool mine = g0 + tid < G;
                 if (g0 > 0) {                             // more groups than threads: direct loads
@@ -399,14 +399,14 @@ __global__ __launch_bounds__(kFxT, 4) void k_Pt_tiles_fixed(
                 double v[4], t1[4], t2[4];
 #pragma unroll
                 for (int m = 0; m < 4; ++m) {
-                    const uint32_t off = (w[m] >> 16) & 0xFFFu;
+                    const uint32_t off = (w[m] >> kFxOffsetShift) & kFxOffsetMask;
                     v[m] = vbuf[w[m] != kFxNull ? off : 0];
                     t1[m] = t2[m] = 0.0;
                     terms(w[m], a[m], bs[m], v[m], t1[m], t2[m]);
                 }
-                const int level = mine ? (int)((w[0] >> 28) & 15u) : 0;
+                const int level = mine ? (int)((w[0] >> kFxLevelShift) & kFxLevelMask) : 0;
                 if (g0 == 0 && ntail > 0) {
-                    const int64_t tr0 = (int64_t)(m0.y & 0x0FFFFFFFu);
+                    const int64_t tr0 = (int64_t)(m0.y & kFxRunMask);
                     // runs too long for the groups: one thread walks a whole run ...
                     for (uint32_t r = tid; r < ntail; r += kFxT) {
                         const uint2 r0 = trun[tr0 + r], r1 = trun[tr0 + r + 1];
@@ -414,7 +414,7 @@ __global__ __launch_bounds__(kFxT, 4) void k_Pt_tiles_fixed(
                         const int q = (int)r0.y;
                         for (uint32_t e = r0.x; e < r1.x; ++e) {
                             const uint32_t we = tent[e];
-                            const double ve = vbuf[(we >> 16) & 0xFFFu];
+                            const double ve = vbuf[(we >> kFxOffsetShift) & kFxOffsetMask];
                             double u1 = 0.0, u2 = 0.0;
                             terms(we, ANG ? ta[e] : 0.0, TWO ? tb[e] : 0.0, ve, u1, u2);
                             tile_add(q, ve, u1, u2);
@@ -436,7 +436,7 @@ __global__ __launch_bounds__(kFxT, 4) void k_Pt_tiles_fixed(
                             double sv = 0.0, s1 = 0.0, s2 = 0.0;
                             for (uint32_t e = e0; e < e1; ++e) {
                                 const uint32_t we = tent[e];
-                                const double ve = vbuf[(we >> 16) & 0xFFFu];
+                                const double ve = vbuf[(we >> kFxOffsetShift) & kFxOffsetMask];
                                 double u1 = 0.0, u2 = 0.0;
                                 terms(we, ANG ? ta[e] : 0.0, TWO ? tb[e] : 0.0, ve, u1, u2);
                                 sv += ve;
@@ -610,426 +610,25 @@ __global__ __launch_bounds__(256) void k_hot_combine(const int64_t *__restrict__
     }
 }
 
-// ------------------------------------------------------------------- plan -----------
-// keys of the per-slice sort: (global slice number << 16) | pixel in tile; value = list entry
-__global__ __launch_bounds__(256) void k_fx_keys(int64_t nvalid, int64_t ntiles, int S, uint32_t qmask,
-                                                  const int64_t *__restrict__ tile_off,
-                                                  const int64_t *__restrict__ tile_slice0,
-                                                  const uint16_t *__restrict__ pl,
-                                                  uint64_t *__restrict__ keys,
-                                                  uint32_t *__restrict__ vals)
-{
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < nvalid; k += stride) {
-        int64_t lo = 0, hi = ntiles;                      // largest b with tile_off[b] <= k
-        while (hi - lo > 1) {
-            const int64_t mid = (lo + hi) >> 1;
-            if (tile_off[mid] <= k) lo = mid; else hi = mid;
-        }
-        const int64_t r = k - tile_off[lo];
-        const uint32_t w = pl[k];
-        keys[k] = ((uint64_t)(tile_slice0[lo] + r / S) << 16) | (uint64_t)(w & qmask);
-        vals[k] = w | ((uint32_t)(r % S) << 16);
-    }
-}
-
-// One thread per slice walks the slice's sorted entries and packs the runs into groups.
-// WRITE = false: counts[4 s + {0, 1, 2, 3}] = groups, tail runs, tail entries, highest level.
-// WRITE = true: the groups / tail lists are written at the offsets of the slice.
-// NANG = angle arrays to carry along: 0 (pol = 1), 1 (half angle), 2 (cos and sin); a compile-time
-// switch, because a run-time "if (ga)" does not keep the compiler from issuing the a_tb load.
-template <bool WRITE, int NANG>
-__global__ __launch_bounds__(64) void k_fx_pack(
-    int64_t nslices, uint32_t qmask, const int64_t *__restrict__ slice_k0,
-    const uint32_t *__restrict__ ent, const double *__restrict__ a_tb,
-    const double *__restrict__ b_tb, uint32_t *__restrict__ counts,
-    const uint2 *__restrict__ meta, const uint32_t *__restrict__ tent_off,
-    uint32_t *__restrict__ gent, double *__restrict__ ga, double *__restrict__ gb,
-    uint2 *__restrict__ trun, uint32_t *__restrict__ tent, double *__restrict__ ta,
-    double *__restrict__ tb)
-{
-    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= nslices) return;
-    const int64_t k0 = slice_k0[s];
-    const int len = (int)(slice_k0[s + 1] - k0);
-    int64_t g = WRITE ? (int64_t)meta[s].x : 0;
-    uint32_t ntr = 0, nte = 0, ng = 0, maxlev = 0;
-    int fill = 0;
-    auto put = [&](int slot, uint32_t w, uint32_t level) {
-        if (!WRITE) return;
-        const int64_t at = 4 * g + slot;
-        gent[at] = w | (level << 28);
-        const int64_t src = k0 + (int64_t)((w >> 16) & 0xFFFu);
-        if (NANG >= 1) ga[at] = a_tb[src];
-        if (NANG == 2) gb[at] = b_tb[src];
-    };
-    auto close = [&]() {
-        if (WRITE)
-            for (int slot = fill; slot < 4; ++slot) {
-                gent[4 * g + slot] = kFxNull;
-                if (NANG >= 1) ga[4 * g + slot] = 0.0;
-                if (NANG == 2) gb[4 * g + slot] = 0.0;
-            }
-        ++g;
-        ++ng;
-        fill = 0;
-    };
-    int i = 0;
-    while (i < len) {
-        const uint32_t q = ent[k0 + i] & qmask;
-        int L = 1;
-        while (i + L < len && (ent[k0 + i + L] & qmask) == q) ++L;
-        if (L > 4 * (kFxMaxLevel + 1)) {
-            if (WRITE) {
-                const uint32_t e0 = tent_off[s] + nte;
-                trun[(int64_t)(meta[s].y & 0x0FFFFFFFu) + ntr] = make_uint2(e0, q);
-                for (int m = 0; m < L; ++m) {
-                    const uint32_t w = ent[k0 + i + m];
-                    tent[e0 + m] = w;
-                    const int64_t src = k0 + (int64_t)((w >> 16) & 0xFFFu);
-                    if (NANG >= 1) ta[e0 + m] = a_tb[src];
-                    if (NANG == 2) tb[e0 + m] = b_tb[src];
-                }
-            }
-            ++ntr;
-            nte += (uint32_t)L;
-        } else if (L <= 4) {
-            if (fill + L > 4) close();
-            for (int m = 0; m < L; ++m) put(fill + m, ent[k0 + i + m], 0);
-            fill += L;
-            if (fill == 4) close();
-        } else {
-            if (fill > 0) close();
-            if ((uint32_t)((L - 1) / 4) > maxlev) maxlev = (uint32_t)((L - 1) / 4);
-            // all pieces of a run inside ONE wave (64 consecutive groups of the slice): the kernel
-            // orders the pieces by the program order of that wave's LDS adds, not by barriers
-            while ((int)(ng % 64u) + (L + 3) / 4 > 64) close();
-            for (int m = 0; m < L; ++m) {
-                put(fill, ent[k0 + i + m], (uint32_t)(m / 4));
-                if (++fill == 4) close();
-            }
-            if (fill > 0) close();
-        }
-        i += L;
-    }
-    if (fill > 0) close();
-    if (!WRITE) {
-        counts[4 * s] = ng;
-        counts[4 * s + 1] = ntr;
-        counts[4 * s + 2] = nte;
-        counts[4 * s + 3] = maxlev;
-    }
-}
-
-// ---- the same lists built by one workgroup per slice ------------------------------------------------
-// k_fx_keys + a global radix sort + one THREAD per slice walking ~1500 sorted entries (k_fx_pack) cost
-// 14 ms at C4.  k_fx_build does the whole slice in LDS: a bitonic sort of (pixel, position) keys, the
-// runs from a flag scan, and a packing that needs no walk: runs are placed by CLASS with ranks from a
-// scan --
-//   runs of 5 .. 60 entries ("long") first, each in ceil(L / 4) consecutive groups with levels 0, 1, ..;
-//     rows of 64 groups (= one wave of the P^T kernel): with R = 64 - (groups of the slice's longest run)
-//     + 1, run i with u_i = groups of the long runs before it goes to row u_i / R at offset u_i - (u of
-//     the row's first run) <= R - 1, so it ends inside the row;
-//   then the runs of 4, the runs of 3 (slot 3 takes a single), the runs of 2 in pairs (an odd one out
-//     takes two singles), the remaining singles four to a group.
-// What the P^T kernel needs holds as before: a run's entries are in time order, the pieces of a long
-// run are consecutive groups of one wave, a pixel appears in one run per slice.  The sums per pixel
-// are the same sums in the same order as with k_fx_pack's lists; only the packing differs (a few
-// per cent fewer groups: k_fx_pack closes a group when the next run does not fit).
-// Pass 1 (WRITE = false) sorts, stores the sorted keys in ent and counts; pass 2 reads ent and writes.
-constexpr int kFbT = 256, kFbMaxS = 4 * kFxT, kFbPer = kFbMaxS / kFbT;
-constexpr int kFbMaxGroups = 1280;       // 2048 entries: <= 0.4 groups an entry (runs of 5) x 64 / 50
-
-__device__ __forceinline__ uint64_t fb_exscan(uint64_t v, uint64_t *tmp, uint64_t &total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint64_t inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint64_t up = __shfl_up((unsigned long long)inc, d);
-        if (lane >= d) inc += up;
-    }
-    if (lane == 63) tmp[wave] = inc;
-    __syncthreads();
-    uint64_t before = inc - v;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < kFbT / 64; ++w) {
-        if (w < wave) before += tmp[w];
-        total += tmp[w];
-    }
-    __syncthreads();
-    return before;
-}
-
-template <bool WRITE, int NANG>
-__global__ __launch_bounds__(kFbT) void k_fx_build(
-    int64_t nslices, uint32_t qmask, const int64_t *__restrict__ slice_k0, int k0_stride,
-    const uint16_t *__restrict__ pl, uint32_t *__restrict__ ent, const double *__restrict__ a_tb,
-    const double *__restrict__ b_tb, uint32_t *__restrict__ counts, const uint2 *__restrict__ meta,
-    const uint32_t *__restrict__ tent_off, uint32_t *__restrict__ gent, double *__restrict__ ga,
-    double *__restrict__ gb, uint2 *__restrict__ trun, uint32_t *__restrict__ tent,
-    double *__restrict__ ta, double *__restrict__ tb, unsigned int *__restrict__ overflow)
-{
-    __shared__ uint32_t keys[kFbMaxS];
-    __shared__ uint16_t rs[kFbMaxS + 1];
-    __shared__ uint64_t tmp[kFbT / 64];
-    __shared__ uint32_t rowfirst[64];
-    __shared__ uint32_t misc[2];
-    __shared__ uint32_t tails[2 * (kFbMaxS / (4 * (kFxMaxLevel + 1)) + 2)];   // (first sorted entry, first tail entry) per tail run
-    __shared__ uint32_t stage[WRITE ? 4 * kFbMaxGroups : 4];
-    const int64_t s = blockIdx.x;
-    if (s >= nslices) return;
-    const int t = threadIdx.x;
-    // (k0_stride = 1: slice s = [slice_k0[s], slice_k0[s + 1]); 2: a list of (first, end) pairs)
-    const int64_t k0 = slice_k0[s * k0_stride];
-    const int len = (int)(slice_k0[s * k0_stride + 1] - k0);
-    if (!WRITE) {
-        int NS = 64;
-        while (NS < len) NS <<= 1;
-        for (int i = t; i < NS; i += kFbT) {
-            uint32_t key = 0xFFFFFFFFu;
-            if (i < len) {
-                const uint32_t w = pl[k0 + i];
-                key = ((w & qmask) << 12) | ((uint32_t)i << 1) | ((w & ~qmask & 0xFFFFu) ? 1u : 0u);
-            }
-            keys[i] = key;
-        }
-        __syncthreads();
-        for (int k = 2; k <= NS; k <<= 1)
-            for (int j = k >> 1; j > 0; j >>= 1) {
-                for (int i = t; i < NS / 2; i += kFbT) {
-                    const int lo = ((i & ~(j - 1)) << 1) | (i & (j - 1)), hi = lo | j;
-                    const uint32_t a = keys[lo], b = keys[hi];
-                    const bool asc = (lo & k) == 0;
-                    if ((a > b) == asc) {
-                        keys[lo] = b;
-                        keys[hi] = a;
-                    }
-                }
-                __syncthreads();
-            }
-        for (int i = t; i < len; i += kFbT) ent[k0 + i] = keys[i];
-    } else {
-        for (int i = t; i < len; i += kFbT) keys[i] = ent[k0 + i];
-        __syncthreads();
-    }
-    // ---- runs: rs[r] = first sorted entry of run r ----
-    int nst = 0;
-    bool st[kFbPer];
-#pragma unroll
-    for (int u = 0; u < kFbPer; ++u) {
-        const int j = kFbPer * t + u;
-        st[u] = j < len && (j == 0 || (keys[j] >> 12) != (keys[j - 1] >> 12));
-        nst += st[u] ? 1 : 0;
-    }
-    uint64_t tot = 0;
-    int r0 = (int)fb_exscan((uint64_t)nst, tmp, tot);
-    const int nruns = (int)tot;
-#pragma unroll
-    for (int u = 0; u < kFbPer; ++u)
-        if (st[u]) rs[r0++] = (uint16_t)(kFbPer * t + u);
-    if (t == 0) {
-        rs[nruns] = (uint16_t)len;
-        misc[0] = 0;
-        misc[1] = 0;
-    }
-    if (t < 64) rowfirst[t] = 0xFFFFFFFFu;
-    __syncthreads();
-    // ---- classes and ranks: A = singles | pairs << 12 | triples << 24 | fours << 36,
-    //      B = long groups | tail runs << 12 | tail entries << 24 ----
-    uint64_t sumA = 0, sumB = 0;
-    int L[kFbPer];
-#pragma unroll
-    for (int u = 0; u < kFbPer; ++u) {
-        const int r = kFbPer * t + u;
-        L[u] = r < nruns ? (int)rs[r + 1] - (int)rs[r] : 0;
-        if (L[u] == 0) continue;
-        if (L[u] <= 4) sumA += (uint64_t)1 << (12 * (L[u] - 1));
-        else if (L[u] <= 4 * (kFxMaxLevel + 1)) sumB += (uint64_t)((L[u] + 3) / 4);
-        else sumB += ((uint64_t)1 << 12) | ((uint64_t)L[u] << 24);
-    }
-    uint64_t totA = 0, totB = 0;
-    uint64_t exA = fb_exscan(sumA, tmp, totA);
-    uint64_t exB = fb_exscan(sumB, tmp, totB);
-    const int n1 = (int)(totA & 0xFFF), n2 = (int)((totA >> 12) & 0xFFF), n3 = (int)((totA >> 24) & 0xFFF),
-              n4 = (int)((totA >> 36) & 0xFFF);
-    const int ntr = (int)((totB >> 12) & 0xFFF), nte = (int)(totB >> 24);
-    // rows of the long runs: the row length leaves room for the slice's longest run
-#pragma unroll
-    for (int u = 0; u < kFbPer; ++u)
-        if (L[u] > 4 && L[u] <= 4 * (kFxMaxLevel + 1)) atomicMax(&misc[1], (uint32_t)((L[u] - 1) / 4));
-    __syncthreads();
-    const uint32_t row_len = 64u - misc[1];              // (longest run: misc[1] + 1 groups)
-    {
-        uint64_t b = exB;
-#pragma unroll
-        for (int u = 0; u < kFbPer; ++u) {
-            if (L[u] > 4 && L[u] <= 4 * (kFxMaxLevel + 1)) {
-                const uint32_t uu = (uint32_t)(b & 0xFFF);
-                atomicMin(&rowfirst[uu / row_len], uu);
-                b += (uint64_t)((L[u] + 3) / 4);
-            } else if (L[u] > 4 * (kFxMaxLevel + 1)) {
-                b += ((uint64_t)1 << 12) | ((uint64_t)L[u] << 24);
-            }
-        }
-    }
-    __syncthreads();
-    int pos[kFbPer];
-    {
-        uint64_t b = exB;
-#pragma unroll
-        for (int u = 0; u < kFbPer; ++u) {
-            pos[u] = 0;
-            if (L[u] > 4 && L[u] <= 4 * (kFxMaxLevel + 1)) {
-                const uint32_t uu = (uint32_t)(b & 0xFFF), row = uu / row_len;
-                pos[u] = (int)(64 * row + uu - rowfirst[row]);
-                atomicMax(&misc[0], (uint32_t)(pos[u] + (L[u] + 3) / 4));
-                b += (uint64_t)((L[u] + 3) / 4);
-            } else if (L[u] > 4 * (kFxMaxLevel + 1)) {
-                b += ((uint64_t)1 << 12) | ((uint64_t)L[u] << 24);
-            }
-        }
-    }
-    __syncthreads();
-    const int GL = (int)misc[0], maxlev = (int)misc[1];
-    const int odd2 = n2 & 1;
-    const int s1 = n1 > n3 ? n1 - n3 : 0;
-    const int x2 = odd2 ? (s1 < 2 ? s1 : 2) : 0;
-    const int ng = GL + n4 + n3 + (n2 + 1) / 2 + (s1 - x2 + 3) / 4;
-    if (!WRITE) {
-        if (t == 0) {
-            counts[4 * s] = (uint32_t)ng;
-            counts[4 * s + 1] = (uint32_t)ntr;
-            counts[4 * s + 2] = (uint32_t)nte;
-            counts[4 * s + 3] = (uint32_t)maxlev;
-        }
-        return;
-    }
-    if (ng > kFbMaxGroups) {                              // (cannot happen for S <= 2048; never write past the stage)
-        if (t == 0) atomicOr(overflow, 1u);
-        return;
-    }
-    for (int i = t; i < 4 * ng; i += kFbT) stage[i] = kFxNull;
-    __syncthreads();
-    const int64_t g_base = (int64_t)meta[s].x;
-    const int64_t tr_base = (int64_t)(meta[s].y & 0x0FFFFFFFu);
-    const uint32_t te_base = tent_off[s];
-    {
-        uint64_t a = exA, b = exB;
-        const int G4 = GL, G3 = GL + n4, G2 = G3 + n3, G1 = G2 + (n2 + 1) / 2;
-#pragma unroll
-        for (int u = 0; u < kFbPer; ++u) {
-            if (L[u] == 0) continue;
-            const int j0 = (int)rs[kFbPer * t + u];
-            auto value = [&](int m) {
-                const uint32_t key = keys[j0 + m];
-                return (key >> 12) | ((key & 1u) << 15) | (((key >> 1) & 0x7FFu) << 16);
-            };
-            if (L[u] == 1) {
-                const int sr = (int)(a & 0xFFF);
-                int g, slot;
-                if (sr < n3) {
-                    g = G3 + sr;
-                    slot = 3;
-                } else if (sr - n3 < x2) {
-                    g = G2 + n2 / 2;
-                    slot = 2 + (sr - n3);
-                } else {
-                    const int q = sr - n3 - x2;
-                    g = G1 + q / 4;
-                    slot = q % 4;
-                }
-                stage[4 * g + slot] = value(0);
-                a += 1;
-            } else if (L[u] == 2) {
-                const int r2 = (int)((a >> 12) & 0xFFF);
-                const int g = G2 + r2 / 2, slot = (r2 & 1) * 2;
-                stage[4 * g + slot] = value(0);
-                stage[4 * g + slot + 1] = value(1);
-                a += (uint64_t)1 << 12;
-            } else if (L[u] == 3) {
-                const int g = G3 + (int)((a >> 24) & 0xFFF);
-                for (int m = 0; m < 3; ++m) stage[4 * g + m] = value(m);
-                a += (uint64_t)1 << 24;
-            } else if (L[u] == 4) {
-                const int g = G4 + (int)((a >> 36) & 0xFFF);
-                for (int m = 0; m < 4; ++m) stage[4 * g + m] = value(m);
-                a += (uint64_t)1 << 36;
-            } else if (L[u] <= 4 * (kFxMaxLevel + 1)) {
-                for (int m = 0; m < L[u]; ++m)
-                    stage[4 * pos[u] + m] = value(m) | ((uint32_t)(m / 4) << 28);
-                b += (uint64_t)((L[u] + 3) / 4);
-            } else {
-                const int tr = (int)((b >> 12) & 0xFFF);
-                const uint32_t e0 = te_base + (uint32_t)(b >> 24);
-                trun[tr_base + tr] = make_uint2(e0, keys[j0] >> 12);
-                tails[2 * tr] = (uint32_t)j0 | ((uint32_t)L[u] << 16);
-                tails[2 * tr + 1] = e0;
-                b += ((uint64_t)1 << 12) | ((uint64_t)L[u] << 24);
-            }
-        }
-    }
-    __syncthreads();
-    // the runs kept out of the groups: their entries, in time order
-    for (int tr = 0; tr < ntr; ++tr) {
-        const int j0 = (int)(tails[2 * tr] & 0xFFFFu), Lr = (int)(tails[2 * tr] >> 16);
-        const uint32_t e0 = tails[2 * tr + 1];
-        for (int m = t; m < Lr; m += kFbT) {
-            const uint32_t key = keys[j0 + m];
-            const uint32_t w = (key >> 12) | ((key & 1u) << 15) | (((key >> 1) & 0x7FFu) << 16);
-            tent[e0 + m] = w;
-            const int64_t src = k0 + (int64_t)((w >> 16) & 0xFFFu);
-            if (NANG >= 1) ta[e0 + m] = a_tb[src];
-            if (NANG == 2) tb[e0 + m] = b_tb[src];
-        }
-    }
-    for (int i = t; i < 4 * ng; i += kFbT) {
-        const uint32_t w = stage[i];
-        gent[4 * g_base + i] = w;
-        const int64_t src = k0 + (int64_t)((w >> 16) & 0xFFFu);
-        if (NANG >= 1) ga[4 * g_base + i] = w == kFxNull ? 0.0 : a_tb[src];
-        if (NANG == 2) gb[4 * g_base + i] = w == kFxNull ? 0.0 : b_tb[src];
-    }
-}
-
-size_t fx_lds_bytes(const cm2_tiles *t, int S)
-{
-    int vpt = (S + kFxT - 1) / kFxT;
-    vpt = vpt <= 2 ? 2 : vpt;
-    return sizeof(double) * ((size_t)t->tp * t->pol + 2 * (size_t)vpt * kFxT + 3 * (size_t)kFxMaxChunks);
-}
-
-void hot_release(cm2_tiles *t)
-{
-    void **ptrs[] = {(void **)&t->d_hot_flag, (void **)&t->d_hot_range, (void **)&t->d_hot_tiles,
-                     (void **)&t->d_hot_partial, (void **)&t->d_hot_range_tile};
-    for (void **q : ptrs) {
-        if (*q) (void)cm2::dev_free(*q);
-        *q = nullptr;
-    }
-    t->hot_tile.clear();
-    t->hot_chunk0.clear();
-}
-
 // one-pixel tiles with at least kHotMin samples, their sample ranges and the scratch of range sums
 int hot_plan(cm2_tiles *t, hipStream_t st)
 {
-    hot_release(t);
+    FxHot &hot = t->hot;
+    hot.reset();
     const policy::HotRanges h = policy::hot_ranges(t->tile_p0, t->tile_off, kHotChunk);
     const std::vector<int64_t> &range = h.range, &tiles = h.tiles;
-    t->hot_tile = h.hot_tile;
-    t->hot_chunk0 = h.hot_chunk0;
-    if (t->hot_tile.empty()) return 0;
-    CM2_HIP(cm2::dev_malloc(&t->d_hot_flag, h.flag.size()));
-    CM2_HIP(cm2::dev_malloc(&t->d_hot_range, sizeof(int64_t) * range.size()));
-    CM2_HIP(cm2::dev_malloc(&t->d_hot_tiles, sizeof(int64_t) * tiles.size()));
-    CM2_HIP(cm2::dev_malloc(&t->d_hot_partial, sizeof(double) * 3 * (range.size() / 2)));
-    CM2_HIP(cm2::upload(t->d_hot_flag, h.flag.data(), h.flag.size(), st));
-    CM2_HIP(cm2::upload(t->d_hot_range, range.data(), sizeof(int64_t) * range.size(), st));
-    CM2_HIP(cm2::upload(t->d_hot_tiles, tiles.data(), sizeof(int64_t) * tiles.size(), st));
-    CM2_HIP(cm2::dev_malloc(&t->d_hot_range_tile, sizeof(int) * h.range_tile.size()));
-    CM2_HIP(cm2::upload(t->d_hot_range_tile, h.range_tile.data(), sizeof(int) * h.range_tile.size(), st));
+    hot.tile = h.hot_tile;
+    hot.chunk0 = h.hot_chunk0;
+    if (hot.tile.empty()) return 0;
+    CM2_HIP(cm2::dev_malloc(&hot.d_flag, h.flag.size()));
+    CM2_HIP(cm2::dev_malloc(&hot.d_range, sizeof(int64_t) * range.size()));
+    CM2_HIP(cm2::dev_malloc(&hot.d_tiles, sizeof(int64_t) * tiles.size()));
+    CM2_HIP(cm2::dev_malloc(&hot.d_partial, sizeof(double) * 3 * (range.size() / 2)));
+    CM2_HIP(cm2::upload(hot.d_flag, h.flag.data(), h.flag.size(), st));
+    CM2_HIP(cm2::upload(hot.d_range, range.data(), sizeof(int64_t) * range.size(), st));
+    CM2_HIP(cm2::upload(hot.d_tiles, tiles.data(), sizeof(int64_t) * tiles.size(), st));
+    CM2_HIP(cm2::dev_malloc(&hot.d_range_tile, sizeof(int) * h.range_tile.size()));
+    CM2_HIP(cm2::upload(hot.d_range_tile, h.range_tile.data(), sizeof(int) * h.range_tile.size(), st));
     CM2_HIP(hipStreamSynchronize(st));
     return 0;
 }
@@ -1038,263 +637,15 @@ template <int POL, bool HALF>
 int hot_launch(const cm2_tiles *t, const double *d_tod_tb, double *d_out, int64_t tile_lo,
                int64_t tile_hi, hipStream_t stream)
 {
-    // hot tiles inside [tile_lo, tile_hi): they are listed in ascending tile order
-    int64_t h0 = 0, h1 = (int64_t)t->hot_tile.size();
-    while (h0 < h1 && t->hot_tile[(size_t)h0] < tile_lo) ++h0;
-    while (h1 > h0 && t->hot_tile[(size_t)h1 - 1] >= tile_hi) --h1;
-    if (h1 <= h0) return 0;
-    const int64_t c0 = t->hot_chunk0[(size_t)h0], c1 = t->hot_chunk0[(size_t)h1];
+    const FxHot &hot = t->hot;
+    const policy::IndexRange h = policy::tiles_in_range(hot.tile, tile_lo, tile_hi);
+    if (h.hi <= h.lo) return 0;
+    const int64_t c0 = hot.chunk0[(size_t)h.lo], c1 = hot.chunk0[(size_t)h.hi];
     k_Pt_hot<POL, HALF><<<(unsigned)(c1 - c0), kHotT, 0, stream>>>(
-        t->d_hot_range, c0, t->d_pl, HALF ? t->d_half : t->d_cos, t->d_sin, d_tod_tb, t->d_hot_partial);
+        hot.d_range, c0, t->d_pl, HALF ? t->d_half : t->d_cos, t->d_sin, d_tod_tb, hot.d_partial);
     CM2_LAUNCH_OK();
-    k_hot_combine<POL><<<(unsigned)(h1 - h0), 256, 0, stream>>>(t->d_hot_tiles, h0, t->d_hot_partial, d_out);
+    k_hot_combine<POL><<<(unsigned)(h.hi - h.lo), 256, 0, stream>>>(hot.d_tiles, h.lo, hot.d_partial, d_out);
     CM2_LAUNCH_OK();
-    return 0;
-}
-
-void fx_release(cm2_tiles *t)
-{
-    hot_release(t);
-    void **ptrs[] = {(void **)&t->d_fx_slice0, (void **)&t->d_fx_sk, (void **)&t->d_fx_meta, (void **)&t->d_fx_gent,
-                     (void **)&t->d_fx_ga, (void **)&t->d_fx_gb, (void **)&t->d_fx_trun,
-                     (void **)&t->d_fx_tent, (void **)&t->d_fx_ta, (void **)&t->d_fx_tb,
-                     (void **)&t->d_parts, (void **)&t->d_multi,
-                     (void **)&t->d_part_buf, (void **)&t->d_fx_fused, (void **)&t->d_fx_count};
-    for (void **q : ptrs) {
-        if (*q) (void)cm2::dev_free(*q);
-        *q = nullptr;
-    }
-    t->tile_part0.clear();
-    t->multi_tile.clear();
-    t->nparts = t->part_slots = 0;
-    t->part_makespan = 0.0;
-    t->fx_S = 0;
-    t->fx_ngroups = t->fx_nslices = 0;
-}
-
-// a tile that k_Pt_hot takes over (hot_plan): its slices do not count when the slice length is tuned
-static bool fx_hot_tile(const cm2_tiles *t, int64_t b)
-{
-    return policy::is_hot_tile(t->tile_p0[(size_t)b + 1] - t->tile_p0[(size_t)b], t->tile_count[(size_t)b]);
-}
-
-// groups per full slice of S samples and the fraction of slices with more groups than threads,
-// from every 8th full slice (k_fx_build's counting pass on ~12 % of the samples): the slice length
-// is chosen from this before anything is allocated or written
-int fx_estimate(const cm2_tiles *t, int S, hipStream_t st, double *mean_groups, double *over)
-{
-    *mean_groups = 0.0;
-    *over = 0.0;
-    std::vector<int64_t> pairs;
-    const policy::Slices sl_all = policy::slices(t->tile_off, S);
-    const std::vector<int64_t> &slice0 = sl_all.slice0, &all = sl_all.pairs;
-    int64_t seen = 0;
-    for (int64_t b = 0; b < t->ntiles; ++b) {
-        if (fx_hot_tile(t, b)) continue;
-        for (int64_t sl = slice0[(size_t)b]; sl < slice0[(size_t)b + 1]; ++sl) {
-            const int64_t k = all[(size_t)(2 * sl)], e = all[(size_t)(2 * sl + 1)];
-            if (e - k != S) continue;                    // (full slices only)
-            if (seen++ % 8 == 0) {
-                pairs.push_back(k);
-                pairs.push_back(e);
-            }
-        }
-    }
-    const int64_t np = (int64_t)pairs.size() / 2;
-    if (np == 0) return 0;
-    DevTemp<int64_t> d_pairs;
-    DevTemp<uint32_t> ent, d_counts;
-    DevTemp<unsigned int> d_overflow;
-    CM2_HIP(d_pairs.alloc(pairs.size()));
-    CM2_HIP(cm2::upload(d_pairs, pairs.data(), sizeof(int64_t) * pairs.size(), st));
-    CM2_HIP(ent.alloc(t->nvalid));
-    CM2_HIP(d_counts.alloc(4 * np));
-    CM2_HIP(d_overflow.alloc(1));
-    k_fx_build<false, 0><<<(unsigned)np, kFbT, 0, st>>>(
-        np, t->half ? 0x7FFFu : 0xFFFFu, d_pairs, 2, t->d_pl, ent, nullptr, nullptr, d_counts, nullptr, nullptr,
-        nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, d_overflow);
-    CM2_LAUNCH_OK();
-    std::vector<uint32_t> counts((size_t)(4 * np));
-    CM2_HIP(cm2::download(counts.data(), d_counts, sizeof(uint32_t) * counts.size(), st));
-    CM2_HIP(hipStreamSynchronize(st));
-    double gsum = 0.0;
-    int64_t nover = 0;
-    for (int64_t i = 0; i < np; ++i) {
-        gsum += counts[(size_t)(4 * i)];
-        if (counts[(size_t)(4 * i)] > (uint32_t)kFxT) ++nover;
-    }
-    *mean_groups = gsum / (double)np;
-    *over = (double)nover / (double)np;
-    return 0;
-}
-
-// builds the lists for slices of S samples; *mean_groups = average groups per full slice,
-// *over = fraction of slices with more groups than threads
-int fx_build(cm2_tiles *t, int S, hipStream_t st, double *mean_groups, double *over)
-{
-    // (k_fx_build sorts a slice in LDS; fx_max_slice allows no longer one)
-    CM2_CHECK(S <= kFbMaxS, "cm2_tiles: a slice of %d samples is longer than the %d the list builder holds", S, kFbMaxS);
-    fx_release(t);
-    const int64_t nv = t->nvalid;
-    policy::Slices sl = policy::slices(t->tile_off, S);
-    const std::vector<int64_t> &slice0 = sl.slice0;
-    std::vector<int64_t> &k0 = sl.pairs;             // k0: (first address, end) of every slice
-    const int64_t nslices = slice0[(size_t)t->ntiles];
-    CM2_CHECK(nslices < ((int64_t)1 << 31), "cm2_tiles: too many slices");
-    {
-        std::vector<uint2> sk((size_t)nslices + 1, make_uint2(0, 0));
-        for (int64_t i = 0; i < nslices; ++i)
-            sk[(size_t)i] = make_uint2((uint32_t)k0[(size_t)(2 * i)], (uint32_t)(k0[(size_t)(2 * i + 1)] - k0[(size_t)(2 * i)]));
-        CM2_HIP(cm2::dev_malloc(&t->d_fx_sk, sizeof(uint2) * sk.size()));
-        CM2_HIP(cm2::upload(t->d_fx_sk, sk.data(), sizeof(uint2) * sk.size(), st));
-        CM2_HIP(hipStreamSynchronize(st));           // (sk is a local)
-    }
-    if (k0.empty()) { k0.push_back(0); k0.push_back(0); }
-    CM2_HIP(cm2::dev_malloc(&t->d_fx_slice0, sizeof(int64_t) * slice0.size()));
-    CM2_HIP(cm2::upload(t->d_fx_slice0, slice0.data(), sizeof(int64_t) * slice0.size(), st));
-    std::vector<uint2> meta((size_t)nslices + 1, make_uint2(0, 0));
-    std::vector<uint32_t> tent_off((size_t)nslices + 1, 0);
-    int64_t ngroups = 0, ntrun = 0, ntent = 0;
-    *mean_groups = 0.0;
-    *over = 0.0;
-    if (nv > 0) {
-        DevTemp<int64_t> d_k0;
-        DevTemp<uint64_t> keys_in, keys_out;
-        DevTemp<uint32_t> vals_in, ent, d_counts, d_tent_off;
-        DevTemp<unsigned int> d_overflow;
-        DevTemp<char> d_temp;
-        CM2_HIP(d_k0.alloc(k0.size()));
-        CM2_HIP(cm2::upload(d_k0, k0.data(), sizeof(int64_t) * k0.size(), st));
-        // one workgroup per slice (k_fx_build) unless CM2_FX_BUILD=serial asks for the radix sort and
-        // the one-thread-per-slice packer (k_fx_pack): other lists, the same sums
-        const bool serial = t->sw.fx_serial;
-        // (k_fx_pack, the serial builder of the global order, reads the slices as a cut list: slice s =
-        //  [cut[s], cut[s + 1]))
-        DevTemp<int64_t> d_k0s;
-        std::vector<int64_t> cuts;
-        if (serial) {
-            for (int64_t i = 0; i < nslices; ++i) cuts.push_back(k0[(size_t)(2 * i)]);
-            cuts.push_back(nv);
-            CM2_HIP(d_k0s.alloc(cuts.size()));
-            CM2_HIP(cm2::upload(d_k0s, cuts.data(), sizeof(int64_t) * cuts.size(), st));
-        }
-        CM2_HIP(ent.alloc(nv));
-        CM2_HIP(d_counts.alloc(4 * nslices));
-        CM2_HIP(d_overflow.alloc(1));
-        CM2_HIP(hipMemsetAsync(d_overflow.p, 0, sizeof(unsigned int), st));
-        const uint32_t qmask = t->half ? 0x7FFFu : 0xFFFFu;
-        const int pgrid = (int)((nslices + 63) / 64);
-        if (serial) {
-            CM2_HIP(keys_in.alloc(nv));
-            CM2_HIP(keys_out.alloc(nv));
-            CM2_HIP(vals_in.alloc(nv));
-            k_fx_keys<<<grid_for(nv), kBlock, 0, st>>>(nv, t->ntiles, S, qmask, t->d_tile_off,
-                                                      t->d_fx_slice0, t->d_pl, keys_in, vals_in);
-            CM2_LAUNCH_OK();
-            int end_bit = 17;
-            while (((int64_t)1 << (end_bit - 16)) <= nslices && end_bit < 64) ++end_bit;
-            size_t tb = 0;
-            CM2_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, keys_in.p, keys_out.p, vals_in.p,
-                                                       ent.p, nv, 0, end_bit, st));
-            CM2_HIP(d_temp.alloc(tb + 16));
-            CM2_HIP(hipcub::DeviceRadixSort::SortPairs(d_temp.p, tb, keys_in.p, keys_out.p, vals_in.p,
-                                                       ent.p, nv, 0, end_bit, st));
-            k_fx_pack<false, 0><<<pgrid, 64, 0, st>>>(nslices, qmask, d_k0s, ent, nullptr, nullptr, d_counts,
-                                                   nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                                   nullptr, nullptr, nullptr);
-        } else {
-            k_fx_build<false, 0><<<(unsigned)nslices, kFbT, 0, st>>>(
-                nslices, qmask, d_k0, 2, t->d_pl, ent, nullptr, nullptr, d_counts, nullptr, nullptr, nullptr,
-                nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, d_overflow);
-        }
-        CM2_LAUNCH_OK();
-        std::vector<uint32_t> counts((size_t)(4 * nslices));
-        CM2_HIP(cm2::download(counts.data(), d_counts, sizeof(uint32_t) * counts.size(), st));
-        CM2_HIP(hipStreamSynchronize(st));
-        int64_t nfull = 0, nover = 0;
-        double gsum = 0.0;
-        for (int64_t s = 0; s < nslices; ++s) {
-            // .y = first tail run | highest level of the slice << 28
-            meta[(size_t)s] = make_uint2((uint32_t)ngroups,
-                                         (uint32_t)ntrun | (counts[(size_t)(4 * s + 3)] << 28));
-            tent_off[(size_t)s] = (uint32_t)ntent;
-            ngroups += counts[(size_t)(4 * s)];
-            ntrun += counts[(size_t)(4 * s + 1)];
-            ntent += counts[(size_t)(4 * s + 2)];
-        }
-        int64_t ncounted = 0;
-        for (int64_t b = 0; b < t->ntiles; ++b) {
-            if (fx_hot_tile(t, b)) continue;
-            for (int64_t s = slice0[(size_t)b]; s < slice0[(size_t)b + 1]; ++s) {
-                ++ncounted;
-                if (counts[(size_t)(4 * s)] > (uint32_t)kFxT) ++nover;
-                if (k0[(size_t)(2 * s + 1)] - k0[(size_t)(2 * s)] == S) {
-                    ++nfull;
-                    gsum += counts[(size_t)(4 * s)];
-                }
-            }
-        }
-        meta[(size_t)nslices] = make_uint2((uint32_t)ngroups, (uint32_t)ntrun);
-        tent_off[(size_t)nslices] = (uint32_t)ntent;
-        CM2_CHECK(ngroups < ((int64_t)1 << 32) && ntent < ((int64_t)1 << 32) &&
-                  ntrun < ((int64_t)1 << 28), "cm2_tiles: fixed-order lists exceed their offsets");
-        *mean_groups = nfull ? gsum / (double)nfull : 0.0;
-        *over = ncounted ? (double)nover / (double)ncounted : 0.0;
-        // (+1 group: a slice without groups at the very end still loads "its" group 0)
-        const int64_t ng1 = ngroups + 1, nt1 = ntent ? ntent : 1;
-        CM2_HIP(cm2::dev_malloc(&t->d_fx_meta, sizeof(uint2) * meta.size()));
-        CM2_HIP(cm2::upload(t->d_fx_meta, meta.data(), sizeof(uint2) * meta.size(), st));
-        CM2_HIP(d_tent_off.alloc(tent_off.size()));
-        CM2_HIP(cm2::upload(d_tent_off, tent_off.data(), sizeof(uint32_t) * tent_off.size(), st));
-        CM2_HIP(cm2::dev_malloc(&t->d_fx_gent, sizeof(uint4) * ng1));
-        CM2_HIP(cm2::dev_malloc(&t->d_fx_trun, sizeof(uint2) * (ntrun + 1)));
-        CM2_HIP(cm2::dev_malloc(&t->d_fx_tent, sizeof(uint32_t) * nt1));
-        if (t->pol > 1) {
-            CM2_HIP(cm2::dev_malloc(&t->d_fx_ga, sizeof(double) * 4 * ng1));
-            CM2_HIP(cm2::dev_malloc(&t->d_fx_ta, sizeof(double) * nt1));
-            if (!t->half) {
-                CM2_HIP(cm2::dev_malloc(&t->d_fx_gb, sizeof(double) * 4 * ng1));
-                CM2_HIP(cm2::dev_malloc(&t->d_fx_tb, sizeof(double) * nt1));
-            }
-        }
-        const uint2 last = make_uint2((uint32_t)ntent, 0);
-        CM2_HIP(cm2::upload(t->d_fx_trun + ntrun, &last, sizeof(uint2), st));
-#define CM2_FX_PACK(NANG)                                                                       \
-    do {                                                                                        \
-        if (serial)                                                                             \
-            k_fx_pack<true, NANG><<<pgrid, 64, 0, st>>>(                                          \
-                nslices, qmask, d_k0s, ent, t->half ? t->d_half : t->d_cos,                      \
-                t->half ? nullptr : t->d_sin, nullptr, t->d_fx_meta, d_tent_off,                \
-                reinterpret_cast<uint32_t *>(t->d_fx_gent), t->d_fx_ga, t->d_fx_gb, t->d_fx_trun, \
-                t->d_fx_tent, t->d_fx_ta, t->d_fx_tb);                                          \
-        else                                                                                    \
-            k_fx_build<true, NANG><<<(unsigned)nslices, kFbT, 0, st>>>(                           \
-                nslices, qmask, d_k0, 2, t->d_pl, ent, t->half ? t->d_half : t->d_cos,              \
-                t->half ? nullptr : t->d_sin, nullptr, t->d_fx_meta, d_tent_off,                \
-                reinterpret_cast<uint32_t *>(t->d_fx_gent), t->d_fx_ga, t->d_fx_gb, t->d_fx_trun, \
-                t->d_fx_tent, t->d_fx_ta, t->d_fx_tb, d_overflow);                              \
-    } while (0)
-        if (t->pol == 1) CM2_FX_PACK(0);
-        else if (t->half) CM2_FX_PACK(1);
-        else CM2_FX_PACK(2);
-#undef CM2_FX_PACK
-        CM2_LAUNCH_OK();
-        unsigned int h_over = 0;
-        CM2_HIP(cm2::download(&h_over, d_overflow.p, sizeof(h_over), st));
-        CM2_HIP(hipStreamSynchronize(st));
-        CM2_CHECK(h_over == 0, "cm2_tiles: a slice of %d samples packs into more than %d groups", S,
-                  kFbMaxGroups);
-    } else {
-        CM2_HIP(cm2::dev_malloc(&t->d_fx_meta, sizeof(uint2) * meta.size()));
-        CM2_HIP(cm2::upload(t->d_fx_meta, meta.data(), sizeof(uint2) * meta.size(), st));
-        CM2_HIP(cm2::dev_malloc(&t->d_fx_gent, sizeof(uint4)));
-        CM2_HIP(cm2::dev_malloc(&t->d_fx_trun, sizeof(uint2)));
-        CM2_HIP(cm2::dev_malloc(&t->d_fx_tent, sizeof(uint32_t)));
-        CM2_HIP(hipStreamSynchronize(st));
-    }
-    t->fx_S = S;
-    t->fx_ngroups = ngroups;
-    t->fx_nslices = nslices;
     return 0;
 }
 
@@ -1304,27 +655,28 @@ int fx_build(cm2_tiles *t, int S, hipStream_t st, double *mean_groups, double *o
 // CM2_PT_PARTS=<samples> fixes the target); here they become the plan's part lists and scratch.
 int parts_plan(cm2_tiles *t, hipStream_t st)
 {
-    if (!t->pt_split || t->fx_nslices == 0) return 0;
-    const std::vector<int64_t> slice0 = policy::slices(t->tile_off, t->fx_S).slice0;
-    // (two workgroups per CU of the simulated machine when their LDS fits twice, fx_max_slice)
-    const int slots = (fx_lds_bytes(t, t->fx_S) <= 79 * 1024 ? 2 : 1) * policy::kSimCUs;
+    FxParts &pp = t->parts;
+    if (!t->pt_split || t->fx.nslices == 0) return 0;
+    const std::vector<int64_t> slice0 = policy::slices(t->tile_off, t->fx.S).slice0;
+    // (two workgroups per CU of the simulated machine when their LDS fits twice, policy::fx_max_slice)
+    const int slots = policy::fx_workgroups_per_cu(t->tp, t->pol, t->fx.S) * policy::kSimCUs;
     std::vector<int64_t> load((size_t)t->ntiles, 0), nslices((size_t)t->ntiles, 0);
     for (int64_t b = 0; b < t->ntiles; ++b) {
         nslices[(size_t)b] = slice0[(size_t)b + 1] - slice0[(size_t)b];
         if (!fx_hot_tile(t, b)) load[(size_t)b] = t->tile_count[(size_t)b];
     }
-    const policy::PartsChoice choice = policy::choose_parts(load, nslices, t->fx_S, slots, t->sw.pt_parts);
+    const policy::PartsChoice choice = policy::choose_parts(load, nslices, t->fx.S, slots, t->sw.pt_parts);
     if (choice.target == 0) return 0;
     // the parts in tile order (= dispatch order), their scratch slots (split tiles only)
     std::vector<int4> parts;
     std::vector<int64_t> multi;
-    t->tile_part0.assign((size_t)t->ntiles + 1, 0);
+    pp.tile_part0.assign((size_t)t->ntiles + 1, 0);
     int64_t slot = 0;
     for (int64_t b = 0; b < t->ntiles; ++b) {
-        t->tile_part0[(size_t)b] = (int64_t)parts.size();
+        pp.tile_part0[(size_t)b] = (int64_t)parts.size();
         const int64_t s0 = slice0[(size_t)b], ns = nslices[(size_t)b], k = choice.parts[(size_t)b];
         if (k > 1) {
-            t->multi_tile.push_back(b);
+            pp.multi_tile.push_back(b);
             multi.push_back(t->tile_p0[(size_t)b] * t->pol);
             multi.push_back((t->tile_p0[(size_t)b + 1] - t->tile_p0[(size_t)b]) * t->pol);
             multi.push_back(slot);
@@ -1336,19 +688,19 @@ int parts_plan(cm2_tiles *t, hipStream_t st)
         }
         if (k > 1) slot += k;
     }
-    t->tile_part0[(size_t)t->ntiles] = (int64_t)parts.size();
-    if (t->multi_tile.empty()) {                            // nothing to split after all
-        t->tile_part0.clear();
+    pp.tile_part0[(size_t)t->ntiles] = (int64_t)parts.size();
+    if (pp.multi_tile.empty()) {                            // nothing to split after all
+        pp.tile_part0.clear();
         return 0;
     }
-    t->nparts = (int64_t)parts.size();
-    t->part_slots = slot;
-    t->part_makespan = choice.makespan;
-    CM2_HIP(cm2::dev_malloc(&t->d_parts, sizeof(int4) * parts.size()));
-    CM2_HIP(cm2::dev_malloc(&t->d_multi, sizeof(int64_t) * multi.size()));
-    CM2_HIP(cm2::dev_malloc(&t->d_part_buf, sizeof(double) * (size_t)slot * (size_t)t->tp * (size_t)t->pol));
-    CM2_HIP(cm2::upload(t->d_parts, parts.data(), sizeof(int4) * parts.size(), st));
-    CM2_HIP(cm2::upload(t->d_multi, multi.data(), sizeof(int64_t) * multi.size(), st));
+    pp.nparts = (int64_t)parts.size();
+    pp.slots = slot;
+    pp.makespan = choice.makespan;
+    CM2_HIP(cm2::dev_malloc(&pp.d_parts, sizeof(int4) * parts.size()));
+    CM2_HIP(cm2::dev_malloc(&pp.d_multi, sizeof(int64_t) * multi.size()));
+    CM2_HIP(cm2::dev_malloc(&pp.d_buf, sizeof(double) * (size_t)slot * (size_t)t->tp * (size_t)t->pol));
+    CM2_HIP(cm2::upload(pp.d_parts, parts.data(), sizeof(int4) * parts.size(), st));
+    CM2_HIP(cm2::upload(pp.d_multi, multi.data(), sizeof(int64_t) * multi.size(), st));
     CM2_HIP(hipStreamSynchronize(st));
     return 0;
 }
@@ -1358,24 +710,25 @@ int parts_plan(cm2_tiles *t, hipStream_t st)
 // launch).  CM2_PT_FUSE=0 keeps the separate kernels.
 int fused_plan(cm2_tiles *t, hipStream_t st)
 {
+    FxHot &hot = t->hot;
     if (!t->sw.pt_fuse) return 0;
-    const size_t nhot = t->hot_tile.size();
+    const size_t nhot = hot.tile.size();
     if (nhot == 0) return 0;
-    t->fx_count_bytes = (sizeof(unsigned int) * nhot + 15) / 16 * 16;
-    CM2_HIP(cm2::dev_malloc(&t->d_fx_count, t->fx_count_bytes));
+    hot.count_bytes = (sizeof(unsigned int) * nhot + 15) / 16 * 16;
+    CM2_HIP(cm2::dev_malloc(&hot.d_count, hot.count_bytes));
     FxFused z;
     memset(&z, 0, sizeof(z));
-    z.count = t->d_fx_count;
-    z.hot_range = t->d_hot_range;
-    z.hot_range_tile = t->d_hot_range_tile;
-    z.hot_tiles = t->d_hot_tiles;
-    z.hot_partial = t->d_hot_partial;
+    z.count = hot.d_count;
+    z.hot_range = hot.d_range;
+    z.hot_range_tile = hot.d_range_tile;
+    z.hot_tiles = hot.d_tiles;
+    z.hot_partial = hot.d_partial;
     z.pl = t->d_pl;
     z.a_tb = t->d_half ? t->d_half : t->d_cos;
     z.b_tb = t->d_sin;
     FxFused *dz = nullptr;
     CM2_HIP(cm2::dev_malloc(&dz, sizeof(FxFused)));
-    t->d_fx_fused = dz;
+    hot.d_fused = dz;
     CM2_HIP(cm2::upload(dz, &z, sizeof(FxFused), st));
     CM2_HIP(hipStreamSynchronize(st));
     return 0;
@@ -1385,47 +738,45 @@ template <int POL, bool HALF, int VPT>
 int fx_launch_inst(const cm2_tiles *t, const double *d_tod_tb, double *d_out, int64_t tile_lo,
                    int64_t tile_hi, hipStream_t stream)
 {
+    const FxLists &f = t->fx;
+    const FxParts &pp = t->parts;
+    const FxHot &hot = t->hot;
     // plans with parts (and not the exact order): the workgroups are the parts of the tiles in range, in
     // tile (= address) order; then the copies of the split tiles are added up
-    const bool parts = t->d_parts && t->pt_fixed != 2;
-    const int64_t q0 = parts ? t->tile_part0[(size_t)tile_lo] : tile_lo;
-    const int64_t q1 = parts ? t->tile_part0[(size_t)tile_hi] : tile_hi;
+    const bool parts = pp.d_parts && t->pt_fixed != 2;
+    const int64_t q0 = parts ? pp.tile_part0[(size_t)tile_lo] : tile_lo;
+    const int64_t q1 = parts ? pp.tile_part0[(size_t)tile_hi] : tile_hi;
     // fused form: the hot tiles' ranges inside [tile_lo, tile_hi) are further workgroups of this launch
-    const bool fused = t->d_fx_fused && t->pt_fixed != 2;
+    const bool fused = hot.d_fused && t->pt_fixed != 2;
     int64_t hc0 = 0, hc1 = 0;
-    if (fused && t->d_hot_flag) {
-        int64_t h0 = 0, h1 = (int64_t)t->hot_tile.size();
-        while (h0 < h1 && t->hot_tile[(size_t)h0] < tile_lo) ++h0;
-        while (h1 > h0 && t->hot_tile[(size_t)h1 - 1] >= tile_hi) --h1;
-        hc0 = t->hot_chunk0[(size_t)h0];
-        hc1 = t->hot_chunk0[(size_t)h1];
+    if (fused && hot.d_flag) {
+        const policy::IndexRange h = policy::tiles_in_range(hot.tile, tile_lo, tile_hi);
+        hc0 = hot.chunk0[(size_t)h.lo];
+        hc1 = hot.chunk0[(size_t)h.hi];
     }
-    size_t lds = fx_lds_bytes(t, t->fx_S);
+    size_t lds = policy::fx_lds_bytes(t->tp, t->pol, f.S);
     if (hc1 > hc0 && lds < sizeof(double) * (3 * (size_t)kHotT + 2)) lds = sizeof(double) * (3 * (size_t)kHotT + 2);
     static size_t granted[64] = {0};
     CM2_HIP(ensure_dynamic_lds((const void *)k_Pt_tiles_fixed<POL, HALF, VPT>, lds, granted));
-    if (fused) CM2_HIP(hipMemsetAsync(t->d_fx_count, 0, t->fx_count_bytes, stream));
+    if (fused) CM2_HIP(hipMemsetAsync(hot.d_count, 0, hot.count_bytes, stream));
     k_Pt_tiles_fixed<POL, HALF, VPT><<<(int)(q1 - q0 + hc1 - hc0), kFxT, lds, stream>>>(
-        t->tp, t->d_tile_p0, (int)tile_lo, t->d_fx_sk, t->d_fx_slice0, t->d_fx_meta,
-        t->d_fx_gent, reinterpret_cast<const double2 *>(t->d_fx_ga),
-        reinterpret_cast<const double2 *>(t->d_fx_gb), t->d_fx_trun, t->d_fx_tent, t->d_fx_ta,
-        t->d_fx_tb, d_tod_tb, d_out,
+        t->tp, t->d_tile_p0, (int)tile_lo, f.d_sk, f.d_slice0, f.d_meta,
+        f.d_gent, reinterpret_cast<const double2 *>(f.d_ga),
+        reinterpret_cast<const double2 *>(f.d_gb), f.d_trun, f.d_tent, f.d_ta,
+        f.d_tb, d_tod_tb, d_out,
         t->pt_fixed == 2 ? 0xFFFFFFFFu : (uint32_t)kFxChunkMinDefault,
-        t->pt_fixed == 2 ? nullptr : t->d_hot_flag, parts ? t->d_parts : nullptr, (int)q0, t->d_part_buf,
-        fused ? static_cast<const FxFused *>(t->d_fx_fused) : nullptr, (int)(q1 - q0), hc0);
+        t->pt_fixed == 2 ? nullptr : hot.d_flag, parts ? pp.d_parts : nullptr, (int)q0, pp.d_buf,
+        fused ? static_cast<const FxFused *>(hot.d_fused) : nullptr, (int)(q1 - q0), hc0);
     CM2_LAUNCH_OK();
     if (parts) {
-        int64_t m0 = 0, m1 = (int64_t)t->multi_tile.size();
-        while (m0 < m1 && t->multi_tile[(size_t)m0] < tile_lo) ++m0;
-        while (m1 > m0 && t->multi_tile[(size_t)m1 - 1] >= tile_hi) --m1;
-        if (m1 > m0) {
-            const dim3 cgrid((unsigned)(m1 - m0), (unsigned)(((int64_t)t->tp * t->pol + 255) / 256));
-            k_parts_combine<<<cgrid, 256, 0, stream>>>(t->d_multi, m0, (int64_t)t->tp * t->pol,
-                                                                     t->d_part_buf, d_out);
+        const policy::IndexRange m = policy::tiles_in_range(pp.multi_tile, tile_lo, tile_hi);
+        if (m.hi > m.lo) {
+            const dim3 cgrid((unsigned)(m.hi - m.lo), (unsigned)(((int64_t)t->tp * t->pol + 255) / 256));
+            k_parts_combine<<<cgrid, 256, 0, stream>>>(pp.d_multi, m.lo, (int64_t)t->tp * t->pol, pp.d_buf, d_out);
             CM2_LAUNCH_OK();
         }
     }
-    if (t->pt_fixed != 2 && t->d_hot_flag && !fused)
+    if (t->pt_fixed != 2 && hot.d_flag && !fused)
         return hot_launch<POL, HALF>(t, d_tod_tb, d_out, tile_lo, tile_hi, stream);
     return 0;
 }
@@ -1434,7 +785,7 @@ template <int POL, bool HALF>
 int fx_launch_vpt(const cm2_tiles *t, const double *d_tod_tb, double *d_out, int64_t tile_lo,
                   int64_t tile_hi, hipStream_t stream)
 {
-    const int vpt = (t->fx_S + kFxT - 1) / kFxT;
+    const int vpt = (t->fx.S + kFxT - 1) / kFxT;
     if (vpt <= 2) return fx_launch_inst<POL, HALF, 2>(t, d_tod_tb, d_out, tile_lo, tile_hi, stream);
     if (vpt == 3) return fx_launch_inst<POL, HALF, 3>(t, d_tod_tb, d_out, tile_lo, tile_hi, stream);
     return fx_launch_inst<POL, HALF, 4>(t, d_tod_tb, d_out, tile_lo, tile_hi, stream);
@@ -1444,55 +795,36 @@ int fx_launch_vpt(const cm2_tiles *t, const double *d_tod_tb, double *d_out, int
 
 namespace cm2 {
 
-void fx_free(cm2_tiles *t) { fx_release(t); }
-
-// longest slice the kernel can stage beside the tile: 4 values a thread at most, and short enough for
-// two workgroups per CU (<= 79 KB each) whenever some slice length allows that
-int fx_max_slice(const cm2_tiles *t)
+void fx_free(cm2_tiles *t)
 {
-    int smax = 4 * kFxT;
-    {
-        int s2 = smax;
-        while (s2 > 2 * kFxT && fx_lds_bytes(t, s2) > 79 * 1024) s2 -= kFxT;
-        if (fx_lds_bytes(t, s2) <= 79 * 1024) smax = s2;
-    }
-    while (smax > 256 && fx_lds_bytes(t, smax) > 159 * 1024) smax -= 256;
-    return smax;
+    t->fx.reset();
+    t->parts.reset();
+    t->hot.reset();
 }
 
 int fx_parts_info(const cm2_tiles *t, int64_t *h_info)
 {
-    h_info[0] = t->d_parts ? t->nparts : t->ntiles;
-    h_info[1] = (int64_t)t->multi_tile.size();
-    h_info[2] = (int64_t)sizeof(double) * (t->part_slots * t->tp * t->pol + (t->hot_chunk0.empty() ? 0 : 3 * t->hot_chunk0.back()));
-    h_info[3] = (int64_t)(1000.0 * t->part_makespan + 0.5);
+    const FxParts &pp = t->parts;
+    h_info[0] = pp.d_parts ? pp.nparts : t->ntiles;
+    h_info[1] = (int64_t)pp.multi_tile.size();
+    h_info[2] = (int64_t)sizeof(double) * (pp.slots * t->tp * t->pol + (t->hot.chunk0.empty() ? 0 : 3 * t->hot.chunk0.back()));
+    h_info[3] = (int64_t)(1000.0 * pp.makespan + 0.5);
     return 0;
 }
 
 int64_t fx_designed_bytes(const cm2_tiles *t)
 {
-    if (!t || !t->fx_S) return 0;
+    if (!t || !t->fx.S) return 0;
     const int64_t per_group = 16 + (t->pol > 1 ? (t->half ? 32 : 64) : 0);
-    return 8 * t->nvalid + per_group * t->fx_ngroups + 8 * t->fx_nslices;
+    return 8 * t->nvalid + per_group * t->fx.ngroups + 8 * t->fx.nslices;
 }
 
 // plan of the fixed-order P^T, built on first use.  Slice length: a slice should fill most of
 // the workgroup's 512 groups but rarely more; the number of groups per sample depends on how
-// often a pixel is hit twice inside a slice, so it is measured: a trial plan with S = 1536 gives
-// the groups per slice, S is then set for ~0.92 x 512 groups and the plan rebuilt
-// (CM2_PT_SLICE = samples fixes S).
-static int fx_plan_build(const cm2_tiles *tc, hipStream_t st, bool *use);
-
+// often a pixel is hit twice inside a slice, so it is measured: a count on a sample of the slices with S = 1536
+// gives the groups per slice, S is then set for ~0.92 x 512 groups and the plan built, and rebuilt while the
+// built lists ask for another length (policy::tune_slice; CM2_PT_SLICE = samples fixes S).
 int fx_plan(const cm2_tiles *tc, hipStream_t st, bool *use)
-{
-    const int rc = fx_plan_build(tc, st, use);
-    // running out of device memory is transient: the failure is not remembered, so that the call may be made
-    // again after the host has freed memory (cosmomap2_amd/_hip.py does that once; a build starts from scratch)
-    if (rc == CM2_ERR_OUT_OF_MEMORY) const_cast<cm2_tiles *>(tc)->fx_failed = 0;
-    return rc;
-}
-
-static int fx_plan_build(const cm2_tiles *tc, hipStream_t st, bool *use)
 {
     cm2_tiles *t = const_cast<cm2_tiles *>(tc);
     *use = false;
@@ -1506,48 +838,45 @@ static int fx_plan_build(const cm2_tiles *tc, hipStream_t st, bool *use)
     if (t->fx_failed) {
         set_error("the fixed-order P^T lists of this tile plan could not be built (earlier error); "
                   "cm2_tiles_set_pt_order(t, 0) selects the atomic form");
-        return 1;
+        return CM2_ERR_HIP;
     }
-    struct FailMark { cm2_tiles *t; bool ok; ~FailMark() { if (!ok) { t->fx_failed = 1; t->fx_S = 0; } } } mark{t, false};
-    if (t->fx_S == 0) {
-        // (4 staged values per thread at most.  Two workgroups per CU need <= 79 KB each: a 2048-pixel
-        // IQU tile (48 KB) with four staged values per thread in two buffers (32 KB) would leave ONE
-        // workgroup per CU (C5: P^T 0.53 -> 0.64 ms); the slice is kept short enough for two whenever
-        // some slice length allows it.)
-        int smax = fx_max_slice(t);
-        if (fx_lds_bytes(t, smax) > 159 * 1024) {        // the tile alone fills LDS: atomics
-            t->pt_fixed = 0;
-            mark.ok = true;
-            return 0;
-        }
-        const int forced = t->sw.pt_slice;
-        double mean = 0.0, over = 0.0;
-        if (forced >= 64 && forced <= 4 * kFxT) {
-            if (int rc = fx_build(t, forced < smax ? forced : smax, st, &mean, &over)) return rc;
-        } else {
-            int S = 1536 < smax ? 1536 : smax;
-            if (!t->sw.fx_serial) {                       // first guess from a sample of the slices
-                if (int rc = fx_estimate(t, S, st, &mean, &over)) return rc;
-                if (mean > 0.0) S = policy::wanted_slice(S, mean, over, smax, kFxT);
+    auto build = [&]() -> int {
+        if (t->fx.S == 0) {
+            // (4 staged values per thread at most.  Two workgroups per CU need <= 79 KB each: a 2048-pixel
+            // IQU tile (48 KB) with four staged values per thread in two buffers (32 KB) would leave ONE
+            // workgroup per CU (C5: P^T 0.53 -> 0.64 ms); the slice is kept short enough for two whenever
+            // some slice length allows it.)
+            if (policy::fx_tile_fills_lds(t->tp, t->pol)) {  // the tile alone fills LDS: atomics
+                t->pt_fixed = 0;
+                return 0;
             }
-            if (int rc = fx_build(t, S, st, &mean, &over)) return rc;
-            for (int iter = 0; iter < 3 && mean > 0.0; ++iter) {
-                const int want = policy::wanted_slice(S, mean, over, smax, kFxT);
-                const bool close_enough = want >= S * 15 / 16 && want <= S * 17 / 16 && over <= 0.10;
-                if (close_enough || want == S) break;
-                S = want;
-                if (int rc = fx_build(t, S, st, &mean, &over)) return rc;
-            }
+            int S = 0;
+            const int rc = policy::tune_slice(
+                t->sw.pt_slice, policy::fx_max_slice(t->tp, t->pol), kFxT, !t->sw.fx_serial,
+                [&](int s, double &mean, double &over) { return fx_count_sample(t, s, st, &mean, &over); },
+                [&](int s, double &mean, double &over) {
+                    fx_free(t);
+                    return fx_build_lists(t, s, st, &mean, &over);
+                },
+                &S);
+            if (rc) return rc;
         }
+        if (!t->hot.d_flag && t->hot.chunk0.empty()) {
+            if (int rc = hot_plan(t, st)) return rc;
+            if (int rc = parts_plan(t, st)) return rc;
+            if (int rc = fused_plan(t, st)) return rc;
+        }
+        *use = true;
+        return 0;
+    };
+    const int rc = build();
+    if (rc) {
+        t->fx.S = 0;
+        // running out of device memory is transient: the failure is not remembered, so that the call may be made
+        // again after the host has freed memory (cosmomap2_amd/_hip.py does that once; a build starts from scratch)
+        if (rc != CM2_ERR_OUT_OF_MEMORY) t->fx_failed = 1;
     }
-    if (!t->d_hot_flag && t->hot_chunk0.empty()) {
-        if (int rc = hot_plan(t, st)) return rc;
-        if (int rc = parts_plan(t, st)) return rc;
-        if (int rc = fused_plan(t, st)) return rc;
-    }
-    mark.ok = true;
-    *use = true;
-    return 0;
+    return rc;
 }
 
 int fx_launch(const cm2_tiles *t, const double *d_tod_tb, double *d_out, int64_t tile_lo,

@@ -603,6 +603,54 @@ def test_fixed_order_lists_built_per_slice_in_lds_give_the_serial_packers_sums(c
         np.testing.assert_array_equal(outs[1], oracle.sparse_rmult(pol, npix, pairs, c, s, v))
 
 
+def test_two_host_threads_applying_pt_on_an_unprepared_plan_build_its_lists_once(cm):
+    """A plan that cm2_tiles_prepare_pt has not seen builds its fixed-order lists inside the first
+    cm2_Pt_tiles_apply, under a lock: two host threads that apply P^T on it at the same moment both
+    succeed, and both get the bits of a prepared plan."""
+    import ctypes
+    import threading
+    from types import SimpleNamespace
+    from cosmomap2_amd import _hip, device as D
+    from cosmomap2_amd.interfaces import linearoperators as L
+    nt, npix, tp, pol = 1 << 20, 12288, 128, 3
+    rng = np.random.default_rng(41)
+    pairs = rng.integers(0, npix, nt)
+    pairs[rng.random(nt) < 0.02] = -1
+    phi = rng.uniform(0, np.pi, nt)
+    v = rng.standard_normal(nt)
+    P = cm.I.SparseLO(npix, nt, pairs, pol=pol, angle_processed=SimpleNamespace(cos=np.cos(2 * phi), sin=np.sin(2 * phi)))
+    T = L._sparse_tiles(P, tile_pixels=tp, slice_samples=4096)            # (prepared)
+    assert T.pt_fixed and T.fixed_order_info()[0] > 0
+    st = D.stream()
+    v_tb, want = D.empty(T.nvalid), D.empty(pol * npix)
+    vd = D.f64(v)
+    _hip.call("cm2_tod_time_to_tiles", T.h, D.ptr(vd), D.ptr(v_tb), st)
+    _hip.call("cm2_Pt_tiles_apply", T.h, D.ptr(v_tb), D.ptr(want), st)
+    h = ctypes.c_void_p()
+    _hip.call("cm2_tiles_create", ctypes.byref(h), D.ptr(P._d_pix), D.ptr(P._d_cos), D.ptr(P._d_sin), nt, npix, pol,
+              tp, 4096, st)
+    U = L._TileHandle(h)                                                  # (not prepared: no lists yet)
+    assert U.pt_fixed and U.fixed_order_info() == (0, 0) and U.nvalid == T.nvalid
+    outs = [D.empty(pol * npix).fill_(5.0) for _ in range(2)]
+    cm.torch.cuda.synchronize()
+    apply_pt, rcs, gate = _hip.load().cm2_Pt_tiles_apply, [None, None], threading.Barrier(2)
+
+    def work(i):
+        gate.wait()
+        rcs[i] = apply_pt(U.h, D.ptr(v_tb), D.ptr(outs[i]), st)
+
+    threads = [threading.Thread(target=work, args=(i,)) for i in range(2)]
+    for th in threads:
+        th.start()
+    for th in threads:
+        th.join()
+    cm.torch.cuda.synchronize()
+    assert rcs == [0, 0], _hip.load().cm2_last_error()
+    assert U.fixed_order_info() == T.fixed_order_info()
+    for out in outs:
+        assert cm.torch.equal(out, want)
+
+
 @pytest.mark.parametrize("pol", [1, 2, 3])
 def test_weights_of_a_hot_pixel_are_summed_in_fixed_chunks(cm, oracle, monkeypatch, pol):
     """ProcessTimeSamples' per-pixel sums (process_ces.py:480-539) are the reference's serial sums

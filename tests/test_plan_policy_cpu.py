@@ -19,6 +19,7 @@ HOT_MIN_FLOOR = 32768         # policy::kHotTileMin
 
 DRIVER = r"""
 #include "cm2_plan_policy.h"
+#include <cctype>
 #include <cstdio>
 #include <cstdlib>
 #include <string>
@@ -97,8 +98,77 @@ static void report(int64_t npix, const std::vector<unsigned int> &hits, int64_t 
     printf("wanted %d %d %d %d\n", wanted_slice(1536, 400.0, 0.0, 2048, 512), wanted_slice(1536, 700.0, 0.3, 2048, 512),
            wanted_slice(1536, 100.0, 0.0, 1536, 512), wanted_slice(1536, 9000.0, 0.0, 2048, 512));
 }
+// ---- the fixed-order lists: LDS budget, list offsets, slice tuning, sub-ranges of an ascending tile list ----
+static int fx_main(int argc, char **argv)
+{
+    const std::string what(argv[1]);
+    if (what == "lds") {                                        // lds <tp> <pol> <S>...
+        const int tp = atoi(argv[2]), pol = atoi(argv[3]);
+        printf("bytes");
+        for (int i = 4; i < argc; ++i) printf(" %lld", (long long)fx_lds_bytes(tp, pol, atoi(argv[i])));
+        printf("\nmax_slice %d\nfills %d\n", fx_max_slice(tp, pol), fx_tile_fills_lds(tp, pol) ? 1 : 0);
+        printf("budgets %lld %lld\n", (long long)kLdsTwoPerCU, (long long)kLdsOnePerCU);
+        printf("per_cu");
+        for (int i = 4; i < argc; ++i) printf(" %d", fx_workgroups_per_cu(tp, pol, atoi(argv[i])));
+        printf("\n");
+        return 0;
+    }
+    if (what == "offsets") {                                    // offsets <S> <threads> <shift>: ntiles, off, hot, counts
+        const int64_t S = atoll(argv[2]);
+        long long n = 0, x;
+        if (scanf("%lld", &n) != 1) return 2;
+        V off((size_t)n + 1, 0);
+        std::vector<uint8_t> hot((size_t)n, 0);
+        for (auto &o : off) { if (scanf("%lld", &x) != 1) return 2; o = x; }
+        for (auto &h : hot) { if (scanf("%lld", &x) != 1) return 2; h = (uint8_t)x; }
+        std::vector<uint32_t> counts;
+        while (scanf("%lld", &x) == 1) counts.push_back((uint32_t)x);
+        const Slices sl = slices(off, S);
+        if ((int64_t)counts.size() != 4 * sl.slice0.back()) return 3;
+        for (int rep = 0; rep < 2; ++rep) {
+            const FxOffsets r = fx_offsets(counts, sl, hot, S, atoi(argv[3]), atoi(argv[4]));
+            put("meta", r.meta);
+            put("tent_off", r.tent_off);
+            printf("totals %lld %lld %lld\nfits %d\nfill %.17g %.17g\n", (long long)r.ngroups, (long long)r.ntrun,
+                   (long long)r.ntent, r.fits ? 1 : 0, r.mean_groups, r.over);
+        }
+        return 0;
+    }
+    if (what == "tune") {                                       // tune <forced> <smax> <sample_first>: (mean, over) answers
+        std::vector<double> ans;
+        double d;
+        while (scanf("%lf", &d) == 1) ans.push_back(d);
+        size_t at = 0;
+        auto step = [&](const char *name) {
+            return [&, name](int S, double &mean, double &over) {
+                printf("%s %d\n", name, S);
+                if (at + 2 > ans.size()) return 9;
+                mean = ans[at++];
+                over = ans[at++];
+                return mean < 0.0 ? 7 : 0;                      // (a negative mean stands for a failed step)
+            };
+        };
+        int S = 0;
+        const int rc = tune_slice(atoi(argv[2]), atoi(argv[3]), 512, atoi(argv[4]) != 0, step("count"), step("build"), &S);
+        printf("rc %d\nS %d\n", rc, S);
+        return 0;
+    }
+    if (what == "range") {                                      // range: list on stdin, then -1, then (lo, hi) pairs
+        V asc, q;
+        long long x;
+        while (scanf("%lld", &x) == 1 && x >= 0) asc.push_back(x);
+        while (scanf("%lld", &x) == 1) q.push_back(x);
+        for (size_t i = 0; i + 1 < q.size(); i += 2) {
+            const IndexRange r = tiles_in_range(asc, q[i], q[i + 1]);
+            printf("%lld %lld\n", (long long)r.lo, (long long)r.hi);
+        }
+        return 0;
+    }
+    return -1;
+}
 int main(int argc, char **argv)
 {
+    if (argc >= 2 && !isdigit((unsigned char)argv[1][0]) && std::string(argv[1]) != "makespan") return fx_main(argc, argv);
     if (argc == 3 && std::string(argv[1]) == "makespan") {      // makespan <slots>: items on stdin
         V items;
         long long x;
@@ -353,3 +423,186 @@ def test_parts_makespan_is_one_for_equal_items_and_grows_with_a_heavier_one(driv
         last = mk
     # one item more than slots: a second round for a single workgroup, which cannot use the whole chip
     assert run(equal + [20000], SLOTS) > 1.3
+
+
+# ---------------------------------------------------------------- the fixed-order lists -------
+def _fx(driver, args, stdin=""):
+    p = subprocess.run([driver] + [str(a) for a in args], input=stdin, stdout=subprocess.PIPE, text=True, check=True)
+    return [ln.split() for ln in p.stdout.splitlines()]
+
+
+TWO_PER_CU, ONE_PER_CU = 79 * 1024, 159 * 1024                # LDS a workgroup may take for two / one to fit a CU
+LDS_S = (64, 1024, 1025, 1536, 2048)
+
+
+def _lds(tp, pol, S):
+    return 8 * (tp * pol + 2 * max(2, -(-S // 512)) * 512 + 384)
+
+
+# ((2304, 3) is the one shape class where only S = 1024 leaves room for two workgroups: the search ends there)
+@pytest.mark.parametrize("tp,pol", [(256, 1), (1024, 3), (2048, 3), (4096, 3), (8192, 3), (16384, 3), (2304, 3)])
+def test_lds_budget_gives_the_longest_slice_that_fits(driver, tp, pol):
+    r = {ln[0]: [int(x) for x in ln[1:]] for ln in _fx(driver, ["lds", tp, pol] + list(LDS_S))}
+    assert r["budgets"] == [TWO_PER_CU, ONE_PER_CU]
+    assert r["bytes"] == [_lds(tp, pol, S) for S in LDS_S]
+    assert r["per_cu"] == [2 if _lds(tp, pol, S) <= TWO_PER_CU else 1 for S in LDS_S]
+    # the longest multiple of 512 (down to 1024) that leaves room for two workgroups a CU, when there is one;
+    # otherwise the longest slice that fits once, going down in steps of 256
+    two = [S for S in (2048, 1536, 1024) if _lds(tp, pol, S) <= TWO_PER_CU]
+    one = [S for S in range(2048, 255, -256) if _lds(tp, pol, S) <= ONE_PER_CU]
+    want = two[0] if two else (one[0] if one else 256)
+    assert r["max_slice"] == [want]
+    assert r["fills"] == [0 if one else 1]                    # "atomics instead" exactly when no slice fits
+    if (tp, pol) == (2048, 3):
+        assert want == 1536
+    if (tp, pol) == (1024, 3):
+        assert want == 2048
+    if (tp, pol) == (16384, 3):
+        assert r["fills"] == [1]
+    if (tp, pol) == (2304, 3):
+        assert want == 1024
+
+
+def _offsets(driver, S, off, hot, counts, threads=512, shift=28):
+    text = " ".join(map(str, [len(hot)] + list(off) + list(hot) + list(np.asarray(counts).ravel())))
+    lines = _fx(driver, ["offsets", S, threads, shift], text)
+    assert lines[:len(lines) // 2] == lines[len(lines) // 2:]  # (no hidden state)
+    return {ln[0]: ln[1:] for ln in lines[:len(lines) // 2]}
+
+
+def test_list_offsets_are_the_running_sums_of_the_counts(driver):
+    rng = np.random.default_rng(5)
+    S, threads = 256, 512
+    # 8 tiles, tile 2 empty, tile 5 flagged hot; ~40 slices, the last one of most tiles shorter than S
+    loads = np.array([5 * S + 17, 3 * S, 0, 7 * S + 1, 4 * S + 200, 9 * S, 6 * S + 64, S - 1])
+    off = np.concatenate([[0], np.cumsum(loads)])
+    hot = np.zeros(8, np.int64)
+    hot[5] = 1
+    ns = -(-loads // S)
+    nslices = int(ns.sum())
+    assert 36 <= nslices <= 44
+    counts = np.stack([rng.integers(300, 700, nslices), rng.integers(0, 4, nslices), rng.integers(0, 900, nslices),
+                       rng.integers(0, 15, nslices)], axis=1)
+    r = _offsets(driver, S, off, hot, counts, threads)
+    meta = np.array([int(x) for x in r["meta"]], np.int64).reshape(-1, 2)
+    tent_off = np.array([int(x) for x in r["tent_off"]], np.int64)
+    ex = np.concatenate([np.zeros((1, 3), np.int64), np.cumsum(counts[:, :3], axis=0)])     # exclusive sums + totals
+    assert len(meta) == nslices + 1 and len(tent_off) == nslices + 1
+    assert np.array_equal(meta[:, 0], ex[:, 0])
+    assert np.array_equal(meta[:, 1] & 0x0FFFFFFF, ex[:, 1])
+    assert np.array_equal(tent_off, ex[:, 2])
+    assert np.array_equal(meta[:-1, 1] >> 28, counts[:, 3]) and meta[-1, 1] >> 28 == 0
+    assert [int(x) for x in r["totals"]] == list(ex[-1]) and r["fits"] == ["1"]
+    # fill statistics over the tiles that are not hot: groups per FULL slice, share of ALL slices over the threads
+    first = np.concatenate([[0], np.cumsum(ns)])
+    gsum, nfull, nover, ncounted = 0.0, 0, 0, 0
+    for b in range(8):
+        if hot[b]:
+            continue
+        for s in range(first[b], first[b + 1]):
+            ncounted += 1
+            nover += int(counts[s, 0] > threads)
+            if min(S, loads[b] - (s - first[b]) * S) == S:
+                nfull += 1
+                gsum += float(counts[s, 0])
+    assert nfull < ncounted and nover > 0
+    assert r["fill"] == ["%.17g" % (gsum / float(nfull)), "%.17g" % (float(nover) / float(ncounted))]
+    # nothing to count: zeros, not a division by zero
+    r = _offsets(driver, S, [0, 0, 0], [0, 0], [])
+    assert r["fill"] == ["0", "0"] and r["totals"] == ["0", "0", "0"] and r["meta"] == ["0", "0"]
+
+
+@pytest.mark.parametrize("column,limit", [(0, 1 << 32), (2, 1 << 32), (1, 1 << 28)])
+@pytest.mark.parametrize("nslices", [3, 4])
+def test_list_offsets_report_each_limit_at_the_limit_and_not_below(driver, column, limit, nslices):
+    S = 64
+    parts = [limit // 2, limit // 2 - 7, 5, 2][:nslices]
+    parts[-1] += limit - sum(parts)                           # the counts of the slices sum to exactly the limit
+    for short, fits in ((0, "0"), (1, "1")):
+        counts = np.zeros((nslices, 4), np.int64)
+        counts[:, column] = parts
+        counts[-1, column] -= short
+        r = _offsets(driver, S, [0, nslices * S], [0], counts)
+        assert [int(x) for x in r["totals"]][(0, 1, 2)[column]] == limit - short
+        assert r["fits"] == [fits]
+
+
+def _wanted(S, mean, over, smax, threads=512):
+    want = int(0.92 * threads * S / mean) // 64 * 64
+    if over > 0.10:
+        want = want if want < S * 7 // 8 else S * 7 // 8 // 64 * 64
+    return max(min(want, smax), 256)
+
+
+def _tune(forced, smax, sample_first, answers):
+    """policy::tune_slice restated: the steps taken, the return code and the last slice length"""
+    ans, steps = list(answers), []
+
+    def step(name, S):
+        steps.append([name, str(S)])
+        mean, over = ans.pop(0)
+        return (7 if mean < 0 else 0), mean, over
+    if 64 <= forced <= 2048:
+        S = min(forced, smax)
+        return steps, step("build", S)[0], S
+    S = min(1536, smax)
+    if sample_first:
+        rc, mean, over = step("count", S)
+        if rc:
+            return steps, rc, S
+        if mean > 0.0:
+            S = _wanted(S, mean, over, smax)
+    rc, mean, over = step("build", S)
+    if rc:
+        return steps, rc, S
+    for _ in range(3):
+        if not mean > 0.0:
+            break
+        want = _wanted(S, mean, over, smax)
+        close_enough = S * 15 // 16 <= want <= S * 17 // 16 and over <= 0.10
+        if close_enough or want == S:
+            break
+        S = want
+        rc, mean, over = step("build", S)
+        if rc:
+            return steps, rc, S
+    return steps, 0, S
+
+
+TUNE = {   # forced, smax, sample first, (mean, over) answers -> the slice lengths built
+    "stops at once, want == S": (0, 1536, 0, [(100.0, 0.0)], [1536]),
+    "stops by close_enough": (0, 2048, 0, [(0.92 * 512 * 1536 / 1500.0, 0.05)], [1536]),
+    "close but many overflow": (0, 2048, 0, [(0.92 * 512 * 1536 / 1500.0, 0.3), (0.92 * 512, 0.0)], [1536, 1344]),
+    "all three rebuilds": (0, 2048, 0, [(900.0, 0.0), (200.0, 0.0), (900.0, 0.0), (200.0, 0.0), (1.0, 0.0)],
+                           [1536, 768, 1792, 896]),
+    "forced, clamped to smax": (2000, 1536, 1, [(300.0, 0.0)], [1536]),
+    "forced": (640, 1536, 1, [(300.0, 0.0)], [640]),
+    "sample first": (0, 2048, 1, [(600.0, 0.0), (471.0, 0.0)], [1152]),
+    "sample of nothing": (0, 1024, 1, [(0.0, 0.0), (0.0, 0.0)], [1024]),
+    "a failed build ends it": (0, 2048, 0, [(900.0, 0.0), (-1.0, 0.0)], [1536, 768]),
+}
+
+
+@pytest.mark.parametrize("case", sorted(TUNE))
+def test_slice_tuning_tries_the_lengths_the_rule_gives(driver, case):
+    forced, smax, sample_first, answers, built = TUNE[case]
+    out = _fx(driver, ["tune", forced, smax, sample_first], " ".join("%r %r" % a for a in answers))
+    steps, rc, S = _tune(forced, smax, sample_first, answers)
+    assert out == steps + [["rc", str(rc)], ["S", str(S)]]
+    assert [int(s[1]) for s in steps if s[0] == "build"] == built and S == built[-1]
+    assert rc == (7 if case.startswith("a failed") else 0)
+    assert ("count" in [s[0] for s in steps]) == (bool(sample_first) and not 64 <= forced <= 2048)
+
+
+def test_tiles_in_range_is_searchsorted_on_the_ascending_list(driver):
+    asc = np.array([3, 4, 9, 17, 18, 40])
+    ranges = [(0, 3), (5, 9), (10, 17), (41, 50), (7, 7),          # empty: before, between, touching, after, no width
+              (4, 18), (9, 10),                                    # inside
+              (3, 41), (3, 40), (4, 41),                           # touching both ends, one end
+              (0, 100)]                                            # everything
+    text = " ".join(map(str, asc)) + " -1 " + " ".join("%d %d" % r for r in ranges)
+    got = [[int(x) for x in ln] for ln in _fx(driver, ["range"], text)]
+    for (lo, hi), (a, e) in zip(ranges, got):
+        assert a == np.searchsorted(asc, lo, "left") and e == max(a, np.searchsorted(asc, hi, "left")), (lo, hi)
+        assert np.array_equal(asc[a:e], asc[(asc >= lo) & (asc < hi)])
+    assert _fx(driver, ["range"], "-1 0 5") == [["0", "0"]]    # an empty list
