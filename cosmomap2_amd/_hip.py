@@ -116,6 +116,18 @@ PROTOTYPES = {
     "cm2_noise_sim_destroy": [_vp],
     "cm2_noise_sim_info": [_vp, ctypes.POINTER(_i64)],
     "cm2_noise_sim_draw": [_vp, _u64, _dbl, _int, _vp, _vp],
+    "cm2_gaps_create": [ctypes.POINTER(_vp), _vp, _int, _i64, ctypes.POINTER(_i64), _i64, ctypes.POINTER(_dbl), _vp],
+    "cm2_gaps_destroy": [_vp],
+    "cm2_gaps_info": [_vp, ctypes.POINTER(_i64)],
+    "cm2_gaps_index": [_vp, _vp, _vp, _vp],
+    "cm2_gaps_gather": [_vp, _vp, _vp, _vp],
+    "cm2_gaps_scatter": [_vp, _vp, _vp, _vp],
+    "cm2_gaps_normal_apply": [_vp, _vp, _vp, _vp, _vp],
+    "cm2_gaps_precond_apply": [_vp, _vp, _vp, _vp],
+    "cm2_gaps_masked_diff": [_vp, _vp, _vp, _vp, _vp],
+    "cm2_gaps_rhs": [_vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "cm2_gaps_finish": [_vp, _vp, _vp, _vp, _vp, _vp],
+    "cm2_gaps_fill_linear": [_vp, _vp, _vp, _i64, _vp],
 }
 _RESTYPE = {"cm2_last_error": ctypes.c_char_p, "cm2_reduce_work_doubles": _i64,
             "cm2_gemm_tn_work_doubles": _i64}
@@ -189,6 +201,8 @@ RESTARTABLE = frozenset([
     "cm2_cutsky_to_fullsky", "cm2_fullsky_to_cutsky", "cm2_ground_bin_sums", "cm2_ground_subtract",
     "cm2_psd_create", "cm2_psd_welch", "cm2_noise_bands_from_psd",
     "cm2_rng_fill", "cm2_noise_filter_from_psd", "cm2_noise_sim_create",
+    "cm2_gaps_create", "cm2_gaps_gather", "cm2_gaps_scatter", "cm2_gaps_normal_apply", "cm2_gaps_precond_apply",
+    "cm2_gaps_masked_diff", "cm2_gaps_rhs", "cm2_gaps_finish", "cm2_gaps_fill_linear",
 ])
 
 

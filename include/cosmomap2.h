@@ -586,6 +586,55 @@ int cm2_noise_sim_info(const cm2_noise_sim *s, int64_t *h_info);
 int cm2_noise_sim_draw(cm2_noise_sim *s, uint64_t realization, double scale, int add, double *d_out,
                        void *stream);
 
+/* ---- n3: the flagged samples of a time stream, and their fill ---------------------------
+ * The reference flags a sample with pix = -1 (flagging_subscan, utilities/IOfiles.py:142-152; the samples of
+ * a masked pixel, process_ces.py:403-418) and has no gap filling: P and P^T skip such samples, ToeplitzLO.mult
+ * (interfaces/linearoperators.py:582-595) does not.  G = the flagged samples, V = the valid ones, Q = N^-1.
+ *
+ * cm2_gaps_create: d_flags holds nt flags, flag_kind 0 = int32 (flagged when negative: the pix array),
+ * 1 = bytes (flagged when non-zero).  The handle KEEPS d_flags: the caller keeps the buffer alive and
+ * unchanged.  Noise blocks of h_sizes[0..nblocks-1] samples (adding up to nt < 2^32 - 1; positions are stored
+ * as uint32).  The handle owns ng and the ascending positions of the flagged samples (a hipCUB select, no sort)
+ * and the table of runs of consecutive flagged samples, cut at the block boundaries.  With h_a0 (a_0 of every
+ * block's band, > 0) it also owns the compact Jacobi vector 1 / a_0(block of the sample) and two buffers of nt
+ * doubles: the scatter target (zeroed here, only its ng flagged positions are ever written again) and the output
+ * of N^-1; h_a0 == NULL makes a handle for cm2_gaps_fill_linear, gather and scatter only.  Synchronises.
+ * cm2_gaps_info: h_info[5] = nt, ng, runs, longest run, bytes of the two buffers.
+ * cm2_gaps_index: h_pos[ng] = the positions (may be NULL), h_runs[3 runs] = (start, length, block) of every run
+ * (may be NULL).  Synchronises.
+ * "Compact" vectors hold ng doubles, the flagged samples in time order. */
+typedef struct cm2_gaps cm2_gaps;
+int cm2_gaps_create(cm2_gaps **out, const void *d_flags, int flag_kind, int64_t nt, const int64_t *h_sizes,
+                    int64_t nblocks, const double *h_a0, void *stream);
+int cm2_gaps_destroy(cm2_gaps *g);
+int cm2_gaps_info(const cm2_gaps *g, int64_t *h_info);
+int cm2_gaps_index(const cm2_gaps *g, uint32_t *h_pos, int64_t *h_runs, void *stream);
+/* d_compact[j] = d_stream[position j];  d_stream[position j] = d_compact[j] (the valid samples of d_stream are
+ * not touched).  Do not synchronise. */
+int cm2_gaps_gather(const cm2_gaps *g, const double *d_stream, double *d_compact, void *stream);
+int cm2_gaps_scatter(const cm2_gaps *g, const double *d_compact, double *d_stream, void *stream);
+/* d_out = Q_GG d_y on compact vectors, (N^-1 scatter(y))_G with `noise` a Toeplitz operator on the same blocks:
+ * scatter into the handle's zero stream, cm2_noise_apply, gather -- one time-order N^-1 plus 2 ng doubles and
+ * 2 ng positions of traffic, no allocation, no synchronisation.  One handle must not run two at once.
+ * cm2_gaps_precond_apply: d_z = d_r / a_0(block), cm2_xmy with the compact Jacobi vector. */
+int cm2_gaps_normal_apply(cm2_gaps *g, cm2_noise *noise, const double *d_y, double *d_out, void *stream);
+int cm2_gaps_precond_apply(const cm2_gaps *g, const double *d_r, double *d_z, void *stream);
+/* d_u[i] = 0 where flagged, d_n[i] - d_d[i] elsewhere (d_n == NULL: n = 0), nt doubles in one pass.  A select:
+ * what d_d holds at a flagged sample never enters arithmetic that is kept.  d_u is neither input.
+ * cm2_gaps_rhs: that, then d_b = (N^-1 u)_G (compact); d_u is nt doubles of scratch. */
+int cm2_gaps_masked_diff(const cm2_gaps *g, const double *d_n, const double *d_d, double *d_u, void *stream);
+int cm2_gaps_rhs(cm2_gaps *g, cm2_noise *noise, const double *d_n, const double *d_d, double *d_u, double *d_b,
+                 void *stream);
+/* d_out[i] = d_d[i] on the valid samples (bit for bit; nothing is moved when d_out == d_d), d_n[i] + d_y[j] at
+ * the j-th flagged sample (d_n == NULL: n = 0). */
+int cm2_gaps_finish(const cm2_gaps *g, const double *d_d, const double *d_n, const double *d_y, double *d_out,
+                    void *stream);
+/* Linear fill: for each run [s, s + len) inside its block, L = mean of the valid samples among the nedge samples
+ * before s inside the block, R = the same for the nedge samples after the run, each summed in time order by one
+ * thread; a side without a valid sample takes the other side's level, both without: 0.  d_out[s + k] =
+ * L + (R - L) (k + 1) / (len + 1); valid samples are copied bit for bit (d_out == d_d: left where they are). */
+int cm2_gaps_fill_linear(const cm2_gaps *g, const double *d_d, double *d_out, int64_t nedge, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
