@@ -128,6 +128,11 @@ PROTOTYPES = {
     "cm2_gaps_rhs": [_vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "cm2_gaps_finish": [_vp, _vp, _vp, _vp, _vp, _vp],
     "cm2_gaps_fill_linear": [_vp, _vp, _vp, _i64, _vp],
+    "cm2_gaps_prepare_tiles": [_vp, _vp, _vp],
+    "cm2_gaps_window_table": [_vp, ctypes.POINTER(_i64), _vp, _vp],
+    "cm2_gaps_tiles_to_time": [_vp, _vp, _vp, _vp, _vp, _vp],
+    "cm2_gaps_time_to_tiles": [_vp, _vp, _vp, _vp, _vp, _vp],
+    "cm2_PtNP_gaps_apply": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
 }
 _RESTYPE = {"cm2_last_error": ctypes.c_char_p, "cm2_reduce_work_doubles": _i64,
             "cm2_gemm_tn_work_doubles": _i64}
@@ -203,6 +208,7 @@ RESTARTABLE = frozenset([
     "cm2_rng_fill", "cm2_noise_filter_from_psd", "cm2_noise_sim_create",
     "cm2_gaps_create", "cm2_gaps_gather", "cm2_gaps_scatter", "cm2_gaps_normal_apply", "cm2_gaps_precond_apply",
     "cm2_gaps_masked_diff", "cm2_gaps_rhs", "cm2_gaps_finish", "cm2_gaps_fill_linear",
+    "cm2_gaps_prepare_tiles", "cm2_gaps_tiles_to_time", "cm2_gaps_time_to_tiles", "cm2_PtNP_gaps_apply",
 ])
 
 

@@ -14,7 +14,15 @@
 // k_gap_scatter (ng writes), cm2_noise_apply, k_gap_gather (ng reads): the positions are ascending and the runs
 // long, so a wave's 64 positions fall in a few cache lines and both kernels move 8-byte words at close to the rate
 // of a contiguous copy.
+//
+// The gap-aware normal operator A_e = [P E]^T N^-1 [P E] (E = one unknown per flagged sample) on a tile plan goes
+// through the time order, because a tile-order stream has no slot for a flagged sample:
+//   k_P_tiles -> k_gap_perm_windows<true> (tile -> time order, g merged in) -> time-order N^-1
+//             -> k_gap_perm_windows<false> (time -> tile order, g read out) -> fixed-order P^T
+// The two permutations are the plan's windowed ones (cm2_tiles.hip) with the flagged samples of a window, the
+// contiguous compact range [c_w, c_{w+1}), written into / read out of the LDS window beside the valid ones.
 #include "cm2_common.h"
+#include "cm2_tiles.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -198,6 +206,82 @@ __global__ __launch_bounds__(256) void k_gap_interp(int64_t ng, int64_t nruns, c
     }
 }
 
+// first[0] = the smallest sample whose flag differs between the tile plan (tb_dst == kInvalidSample) and the flags
+template <int KIND>
+__global__ __launch_bounds__(256) void k_gap_compare(int64_t nt, const void *__restrict__ flags,
+                                                      const uint32_t *__restrict__ tb_dst,
+                                                      uint32_t *__restrict__ first)
+{
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nt; i += stride)
+        if ((tb_dst[i] == kInvalidSample) != is_flagged<KIND>(flags, i)) atomicMin(first, (uint32_t)i);
+}
+
+// cw[w] = number of flagged samples before window w (lower_bound of w kPermWin in pos), w = 0 .. nwin
+__global__ __launch_bounds__(256) void k_gap_window_table(int64_t nwin, int64_t ng, const uint32_t *__restrict__ pos,
+                                                           uint32_t *__restrict__ cw)
+{
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; w <= nwin; w += stride) {
+        const int64_t t0 = w * kPermWin;
+        int64_t lo = 0, hi = ng;                       // pos[j] < t0 for j < lo, pos[j] >= t0 for j >= hi
+        while (lo < hi) {
+            const int64_t mid = (lo + hi) >> 1;
+            if ((int64_t)pos[mid] < t0) lo = mid + 1; else hi = mid;
+        }
+        cw[w] = (uint32_t)lo;
+    }
+}
+
+// k_perm_windows (cm2_tiles.hip) with the flagged samples merged in.  TO_TIME: out[t] = in[tile position of t] on
+// the valid samples and gc[c] at the c-th flagged one -- every slot of a window below its span is one or the
+// other, so nothing is zero-filled (slots from span up are never read).  To tiles: out[tile position] = in[t] and
+// gc[c] = in[pos[c]].  The flagged samples of window w are pos[cw[w] .. cw[w + 1]), read coalesced.
+template <bool TO_TIME>
+__global__ __launch_bounds__(kPermT) void k_gap_perm_windows(int64_t nt, int64_t nwin,
+                                                              const uint32_t *__restrict__ lst_k,
+                                                              const uint16_t *__restrict__ lst_q,
+                                                              const uint32_t *__restrict__ pos,
+                                                              const uint32_t *__restrict__ cw,
+                                                              const double *__restrict__ in, double *__restrict__ out,
+                                                              const double *__restrict__ gc_in,
+                                                              double *__restrict__ gc_out)
+{
+    __shared__ double win[kPermWin];
+    const int per_xcd = (int)((nwin + 7) / 8);
+    const int64_t w = (int64_t)(blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
+    if (w >= nwin) return;
+    const int64_t t0 = w * kPermWin, base = w * kPermWin;
+    const int span = (int)((nt - t0 < kPermWin) ? nt - t0 : kPermWin);
+    const int t = threadIdx.x;
+    const uint32_t c0 = cw[w], c1 = cw[w + 1];
+    uint32_t kk[kPermPer];
+    uint16_t qq[kPermPer];
+#pragma unroll
+    for (int u = 0; u < kPermPer; ++u) {
+        kk[u] = lst_k[base + t + u * kPermT];
+        qq[u] = lst_q[base + t + u * kPermT];
+    }
+    if (TO_TIME) {
+        double vv[kPermPer];
+#pragma unroll
+        for (int u = 0; u < kPermPer; ++u) vv[u] = (kk[u] != kInvalidSample) ? in[kk[u]] : 0.0;
+#pragma unroll
+        for (int u = 0; u < kPermPer; ++u)
+            if (kk[u] != kInvalidSample) win[qq[u]] = vv[u];
+        for (uint32_t c = c0 + t; c < c1; c += kPermT) win[(int64_t)pos[c] - t0] = gc_in[c];
+        __syncthreads();
+        for (int j = t; j < span; j += kPermT) out[t0 + j] = win[j];
+    } else {
+        for (int j = t; j < span; j += kPermT) win[j] = in[t0 + j];
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < kPermPer; ++u)
+            if (kk[u] != kInvalidSample) out[kk[u]] = win[qq[u]];
+        for (uint32_t c = c0 + t; c < c1; c += kPermT) gc_out[c] = win[(int64_t)pos[c] - t0];
+    }
+}
+
 }  // namespace
 
 struct cm2_gaps {
@@ -213,6 +297,11 @@ struct cm2_gaps {
     double *d_jac = nullptr;          // [ng] 1 / a_0 of each flagged sample's block (handles made with h_a0)
     double *d_scatter = nullptr;      // [nt] scatter target: zero on the valid samples     (handles made with h_a0)
     double *d_work = nullptr;         // [nt] N^-1 of it                                     (handles made with h_a0)
+    // cm2_gaps_prepare_tiles: the tile plan whose flagged samples were found equal to the handle's, and for its
+    // windowed permutations the table of the windows' compact ranges
+    uint64_t tiles_plan = 0;          // plan id (0: not prepared)
+    int64_t nwin = 0;                 // windows of the table (0: the plan keeps the per-sample permutations)
+    uint32_t *d_win_c = nullptr;      // [nwin+1] flagged samples before every window; [nwin] = ng
     std::vector<uint32_t> h_run_j0, h_run_start;
     std::vector<int32_t> h_run_blk;
 };
@@ -221,7 +310,7 @@ extern "C" int cm2_gaps_destroy(cm2_gaps *g)
 {
     if (!g) return 0;
     void *ptrs[] = {g->d_off, g->d_pos, g->d_run_j0, g->d_run_start, g->d_run_blk, g->d_run_lr, g->d_jac,
-                    g->d_scatter, g->d_work};
+                    g->d_scatter, g->d_work, g->d_win_c};
     for (void *q : ptrs)
         if (q) (void)cm2::dev_free(q);
     delete g;
@@ -505,4 +594,116 @@ extern "C" int cm2_gaps_fill_linear(const cm2_gaps *g, const double *d_d, double
     k_gap_interp<<<grid_for(g->ng), kBlock, 0, stream>>>(g->ng, g->nruns, g->d_pos, g->d_run_j0, g->d_run_lr, d_out);
     CM2_LAUNCH_OK();
     return 0;
+}
+
+// ------------------------------------------------- the gap-aware normal operator on a tile plan ------
+extern "C" int cm2_gaps_prepare_tiles(cm2_gaps *g, const cm2_tiles *tiles, void *stream_)
+{
+    CM2_CHECK(g && tiles, "cm2_gaps_prepare_tiles: NULL argument");
+    if (g->tiles_plan == tiles->plan_id) return 0;
+    CM2_CHECK(tiles->nt == g->nt, "cm2_gaps_prepare_tiles: the tile plan has nt=%lld samples, the gaps nt=%lld",
+              (long long)tiles->nt, (long long)g->nt);
+    CM2_CHECK(tiles->nvalid + g->ng == g->nt, "cm2_gaps_prepare_tiles: the tile plan has %lld valid samples of "
+              "%lld, the gaps flag %lld: not the same pointing", (long long)tiles->nvalid, (long long)g->nt,
+              (long long)g->ng);
+    hipStream_t stream = as_stream(stream_);
+    DevTemp<uint32_t> d_first;
+    CM2_HIP(d_first.alloc(1));
+    CM2_HIP(hipMemsetAsync(d_first.p, 0xFF, sizeof(uint32_t), stream));
+    if (g->kind == 0)
+        k_gap_compare<0><<<grid_for(g->nt), kBlock, 0, stream>>>(g->nt, g->d_flags, tiles->d_tb_dst, d_first.p);
+    else
+        k_gap_compare<1><<<grid_for(g->nt), kBlock, 0, stream>>>(g->nt, g->d_flags, tiles->d_tb_dst, d_first.p);
+    CM2_LAUNCH_OK();
+    uint32_t first = 0;
+    CM2_HIP(cm2::download(&first, d_first.p, sizeof(first), stream));
+    CM2_CHECK(first == kInvalidSample, "cm2_gaps_prepare_tiles: both flag %lld samples, but sample %u is flagged in "
+              "one and valid in the other: not the same pointing", (long long)g->ng, first);
+    bool windows = false;
+    if (int rc = cm2::perm_lists(tiles, stream, &windows)) return rc;
+    g->tiles_plan = 0;
+    cm2::dev_release(g->d_win_c);
+    g->nwin = 0;
+    if (windows) {
+        const int64_t nwin = tiles->nperm_win;
+        CM2_HIP(cm2::dev_malloc(&g->d_win_c, sizeof(uint32_t) * (nwin + 1)));
+        k_gap_window_table<<<grid_for(nwin + 1), kBlock, 0, stream>>>(nwin, g->ng, g->d_pos, g->d_win_c);
+        CM2_LAUNCH_OK();
+        CM2_HIP(hipStreamSynchronize(stream));
+        g->nwin = nwin;
+    }
+    g->tiles_plan = tiles->plan_id;
+    return 0;
+}
+
+extern "C" int cm2_gaps_window_table(const cm2_gaps *g, int64_t *h_nwin, uint32_t *h_table, void *stream_)
+{
+    CM2_CHECK(g && h_nwin, "cm2_gaps_window_table: NULL argument");
+    *h_nwin = g->nwin;
+    if (h_table && g->nwin)
+        CM2_HIP(cm2::download(h_table, g->d_win_c, sizeof(uint32_t) * (g->nwin + 1), as_stream(stream_)));
+    return 0;
+}
+
+static int gaps_check_tiles(const cm2_gaps *g, const cm2_tiles *tiles, const char *who)
+{
+    CM2_CHECK(g->tiles_plan == tiles->plan_id, "%s: cm2_gaps_prepare_tiles has not been called for this tile plan",
+              who);
+    CM2_CHECK(g->nwin == 0 || (g->nwin == tiles->nperm_win && tiles->d_perm_k && tiles->d_perm_q && g->d_win_c),
+              "%s: the window table does not belong to the plan's lists", who);
+    return 0;
+}
+
+extern "C" int cm2_gaps_tiles_to_time(const cm2_gaps *g, const cm2_tiles *tiles, const double *d_tb,
+                                      const double *d_compact, double *d_time, void *stream_)
+{
+    CM2_CHECK(g && tiles && d_time && (d_tb || tiles->nvalid == 0) && (d_compact || g->ng == 0),
+              "cm2_gaps_tiles_to_time: NULL argument");
+    if (int rc = gaps_check_tiles(g, tiles, "cm2_gaps_tiles_to_time")) return rc;
+    if (!g->nwin) {
+        if (int rc = cm2_tod_tiles_to_time(tiles, d_tb, d_time, stream_)) return rc;
+        return cm2_gaps_scatter(g, d_compact, d_time, stream_);
+    }
+    const int grid = (int)(((g->nwin + 7) / 8) * 8);
+    k_gap_perm_windows<true><<<grid, kPermT, 0, as_stream(stream_)>>>(
+        g->nt, g->nwin, tiles->d_perm_k, tiles->d_perm_q, g->d_pos, g->d_win_c, d_tb, d_time, d_compact, nullptr);
+    CM2_LAUNCH_OK();
+    return 0;
+}
+
+extern "C" int cm2_gaps_time_to_tiles(const cm2_gaps *g, const cm2_tiles *tiles, const double *d_time, double *d_tb,
+                                      double *d_compact_out, void *stream_)
+{
+    CM2_CHECK(g && tiles && d_time && (d_tb || tiles->nvalid == 0) && (d_compact_out || g->ng == 0),
+              "cm2_gaps_time_to_tiles: NULL argument");
+    if (int rc = gaps_check_tiles(g, tiles, "cm2_gaps_time_to_tiles")) return rc;
+    if (!g->nwin) {
+        if (int rc = cm2_gaps_gather(g, d_time, d_compact_out, stream_)) return rc;
+        return cm2_tod_time_to_tiles(tiles, d_time, d_tb, stream_);
+    }
+    const int grid = (int)(((g->nwin + 7) / 8) * 8);
+    k_gap_perm_windows<false><<<grid, kPermT, 0, as_stream(stream_)>>>(
+        g->nt, g->nwin, tiles->d_perm_k, tiles->d_perm_q, g->d_pos, g->d_win_c, d_time, d_tb, nullptr,
+        d_compact_out);
+    CM2_LAUNCH_OK();
+    return 0;
+}
+
+extern "C" int cm2_PtNP_gaps_apply(const cm2_tiles *tiles, cm2_noise *noise, const cm2_gaps *g, const double *d_z,
+                                   double *d_out, double *d_tb, double *d_time1, double *d_time2, void *stream_)
+{
+    CM2_CHECK(tiles && noise && g && d_z && d_out && d_tb && d_time1 && d_time2, "cm2_PtNP_gaps_apply: NULL argument");
+    CM2_CHECK(d_time1 != d_time2 && d_z != d_out, "cm2_PtNP_gaps_apply: d_time1 / d_time2 and d_z / d_out must differ");
+    if (int rc = gaps_check_tiles(g, tiles, "cm2_PtNP_gaps_apply")) return rc;
+    int64_t op[6] = {0, 0, 0, 0, 0, 0};
+    if (int rc = cm2_noise_info(noise, op)) return rc;
+    CM2_CHECK(op[0] == g->nt && op[1] == g->nb && op[2] > 0, "cm2_PtNP_gaps_apply: the noise operator has %lld "
+              "samples in %lld blocks (lambda %lld), the gaps %lld in %lld", (long long)op[0], (long long)op[1],
+              (long long)op[2], (long long)g->nt, (long long)g->nb);
+    const int64_t nmap = (int64_t)tiles->pol * tiles->npix;
+    if (int rc = cm2_P_tiles_apply(tiles, d_z, d_tb, stream_)) return rc;
+    if (int rc = cm2_gaps_tiles_to_time(g, tiles, d_tb, d_z + nmap, d_time1, stream_)) return rc;
+    if (int rc = cm2_noise_apply(noise, d_time1, d_time2, stream_)) return rc;
+    if (int rc = cm2_gaps_time_to_tiles(g, tiles, d_time2, d_tb, d_out + nmap, stream_)) return rc;
+    return cm2_Pt_tiles_apply(tiles, d_tb, d_out, stream_);
 }

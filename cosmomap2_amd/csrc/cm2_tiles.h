@@ -164,5 +164,12 @@ int fx_launch(const cm2_tiles *t, const double *d_tod_tb, double *d_out, int64_t
 void fx_free(cm2_tiles *t);
 int64_t fx_designed_bytes(const cm2_tiles *t);
 int fx_parts_info(const cm2_tiles *t, int64_t *h_info);   // cm2_tiles_pt_parts
+
+// Windowed permutations between time and tile order (cm2_tiles.hip; the forms that merge the flagged samples in:
+// cm2_gaps.hip): a workgroup of kPermT threads owns kPermWin consecutive time samples.  perm_lists builds the
+// plan's address-sorted lists d_perm_k / d_perm_q on first use (allocates, synchronises); *use = false for a
+// TOD shorter than one window, which keeps the per-sample kernels.
+constexpr int kPermWin = 8192, kPermT = 256, kPermPer = kPermWin / kPermT;
+int perm_lists(const cm2_tiles *t, hipStream_t st, bool *use);
 }  // namespace cm2
 

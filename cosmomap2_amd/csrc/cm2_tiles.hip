@@ -539,7 +539,7 @@ __global__ __launch_bounds__(1024) void k_tiles_to_time(int64_t nt, int64_t chun
 // payload.  Here a workgroup owns kPermWin consecutive time samples, reaches their TB
 // positions through a list sorted by address (one contiguous run per tile) and stages the
 // window in LDS, so that both sides of the copy are streams: 6 + 8 + 8 bytes per sample.
-constexpr int kPermWin = 8192, kPermT = 256, kPermPer = kPermWin / kPermT;
+// (kPermWin, kPermT, kPermPer: cm2_tiles.h -- cm2_gaps.hip builds its merging forms on the same lists)
 
 template <bool TO_TIME>
 __global__ __launch_bounds__(kPermT) void k_perm_windows(int64_t nt, int64_t nwin,
@@ -1071,7 +1071,7 @@ static inline void perm_geometry(int64_t nt, int &blocks, int64_t &chunk)
 }
 
 // lists of the windowed permutations (a TOD shorter than one window keeps the per-sample kernels)
-static int perm_lists(const cm2_tiles *tc, hipStream_t st, bool *use)
+int cm2::perm_lists(const cm2_tiles *tc, hipStream_t st, bool *use)
 {
     cm2_tiles *t = const_cast<cm2_tiles *>(tc);         // lazily built cache
     *use = false;

@@ -4,3 +4,4 @@ from .. import linop as lp                                   # noqa: F401
 from .linearoperators import *                               # noqa: F401,F403
 from .blkop import BlockDiagonalLinearOperator               # noqa: F401
 from .deflationlib import *                                  # noqa: F401,F403
+from .gapaware import *                                      # noqa: F401,F403

@@ -635,6 +635,40 @@ int cm2_gaps_finish(const cm2_gaps *g, const double *d_d, const double *d_n, con
  * L + (R - L) (k + 1) / (len + 1); valid samples are copied bit for bit (d_out == d_d: left where they are). */
 int cm2_gaps_fill_linear(const cm2_gaps *g, const double *d_d, double *d_out, int64_t nedge, void *stream);
 
+/* The gap-aware normal operator: one unknown per flagged sample.  With E the nt x ng matrix that has a one at
+ * (position of the j-th flagged sample, j) and P_e = [P E],
+ *     A_e = P_e^T N^-1 P_e = [ P^T Q P   P^T Q E ]      on vectors z = [map (pol npix) ; g (ng, compact)].
+ *                            [ E^T Q P   Q_GG    ]
+ * Eliminating g from A_e z = P_e^T N^-1 d0 (d0 = d on V, 0 on G) leaves (P^T S P) m = P^T S d_V with the Schur
+ * complement S = Q_VV - Q_VG Q_GG^-1 Q_GV, the GLS map of the valid samples alone; g = Q_GG^-1 Q_GV (d_V - P m).
+ * A tile-order stream has no slot for a flagged sample, so on a tile plan the chain goes through the time order:
+ * cm2_P_tiles_apply, tile -> time order with g written into the flagged samples, cm2_noise_apply, time -> tile
+ * order with the flagged samples read out, cm2_Pt_tiles_apply.
+ *
+ * cm2_gaps_prepare_tiles: makes `tiles` the plan of the handle (one at a time, keyed by the plan's id; a call for
+ * the plan already prepared returns at once).  Refuses with CM2_ERR_ARGUMENT a plan with another nt, one whose
+ * valid samples and the handle's flagged ones do not add up to nt, and one whose flagged set differs (a device pass
+ * over the plan's index and the handle's flags; the message names the first sample that differs).  Builds the
+ * plan's windowed permutation lists if they do not exist yet and the table of the windows' compact ranges (windows
+ * of 8192 time samples; window w owns the flagged samples [c_w, c_{w+1}), c_w = the number of positions below
+ * 8192 w).  Allocates and synchronises.  A stream shorter than one window has no table: the per-sample
+ * permutations and cm2_gaps_scatter / cm2_gaps_gather serve.
+ * cm2_gaps_window_table: *h_nwin = windows of the table (0: none), h_table[nwin + 1] = c_w (may be NULL).
+ * cm2_gaps_tiles_to_time: d_time = cm2_tod_tiles_to_time(d_tb) with d_compact written into the flagged samples,
+ * in one kernel; cm2_gaps_time_to_tiles: d_tb = cm2_tod_time_to_tiles(d_time), d_compact_out = the flagged samples
+ * of d_time.  Both bit-equal to the two-call forms; after prepare no allocation and no synchronisation.
+ * cm2_PtNP_gaps_apply: d_out = A_e d_z (pol npix + ng doubles each, d_out != d_z) on `stream`.  Scratch of the
+ * caller: d_tb (valid samples of the plan), d_time1 != d_time2 (nt doubles each).  `noise` is a Toeplitz operator
+ * on the handle's blocks.  After cm2_gaps_prepare_tiles (and cm2_tiles_prepare_pt): kernel launches only. */
+int cm2_gaps_prepare_tiles(cm2_gaps *g, const cm2_tiles *tiles, void *stream);
+int cm2_gaps_window_table(const cm2_gaps *g, int64_t *h_nwin, uint32_t *h_table, void *stream);
+int cm2_gaps_tiles_to_time(const cm2_gaps *g, const cm2_tiles *tiles, const double *d_tb, const double *d_compact,
+                           double *d_time, void *stream);
+int cm2_gaps_time_to_tiles(const cm2_gaps *g, const cm2_tiles *tiles, const double *d_time, double *d_tb,
+                           double *d_compact_out, void *stream);
+int cm2_PtNP_gaps_apply(const cm2_tiles *tiles, cm2_noise *noise, const cm2_gaps *g, const double *d_z,
+                        double *d_out, double *d_tb, double *d_time1, double *d_time2, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
