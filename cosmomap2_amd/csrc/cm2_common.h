@@ -91,6 +91,16 @@ static inline hipError_t ensure_dynamic_lds(const void *func, size_t bytes, size
     return e;
 }
 
+// frees the device buffers it is given and clears the pointers
+template <typename... P>
+inline void dev_release(P *&...p) { ((p ? (void)dev_free(p) : (void)0, p = nullptr), ...); }
+// base of the owners of device state: reset() (and the destructor) of the owner frees what it holds
+struct NoCopy {
+    NoCopy() = default;
+    NoCopy(const NoCopy &) = delete;
+    NoCopy &operator=(const NoCopy &) = delete;
+};
+
 // Scratch allocation of a setup routine: freed on every exit path (the CM2_HIP / CM2_CHECK
 // macros return early on failure).  keep() hands the buffer over to a longer-lived owner.
 template <typename T>

@@ -237,7 +237,7 @@ extern "C" int cm2_release_cached_memory(void)
     if (first != hipSuccess) {
         (void)hipGetLastError();
         cm2::set_error("cm2_release_cached_memory: hipFree failed: %s", hipGetErrorString(first));
-        return 1;
+        return CM2_ERR_HIP;
     }
     return 0;
 }

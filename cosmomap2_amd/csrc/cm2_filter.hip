@@ -6,7 +6,7 @@
 // second read of d comes from L2).  The wave also zero-fills the gap in front of its chunk, so
 // the output needs no separate memset: algorithmic traffic is 8 (d) + 4 (pix) + 8 (out) bytes
 // per sample.  The Legendre tables are shared by all chunks of one length and stay in L2.
-#include "cm2_common.h"
+#include "cm2_tiles.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -590,12 +590,12 @@ int filter_fill(cm2_filter *f, int64_t nt, int64_t nseg, const int64_t *h_start,
     f->d_pix = d_pix;
     f->h_start.assign(h_start, h_start + nseg);
     f->h_len.assign(h_len, h_len + nseg);
-    if (upload(&f->d_start, h_start, (size_t)nseg, st)) return 1;
-    if (upload(&f->d_len, h_len, (size_t)nseg, st)) return 1;
-    if (upload(&f->d_prev_end, prev_end.data(), (size_t)nseg, st)) return 1;
+    if (int rc = upload(&f->d_start, h_start, (size_t)nseg, st)) return rc;
+    if (int rc = upload(&f->d_len, h_len, (size_t)nseg, st)) return rc;
+    if (int rc = upload(&f->d_prev_end, prev_end.data(), (size_t)nseg, st)) return rc;
     if (order > 0) {
-        if (upload(&f->d_toff, h_table_off, (size_t)nseg, st)) return 1;
-        if (upload(&f->d_table, h_table, (size_t)table_len, st)) return 1;
+        if (int rc = upload(&f->d_toff, h_table_off, (size_t)nseg, st)) return rc;
+        if (int rc = upload(&f->d_table, h_table, (size_t)table_len, st)) return rc;
         int rc = 0;
         switch (K) {
             case 2: rc = setup_poly<2>(f, st); break;
@@ -680,11 +680,6 @@ extern "C" int cm2_filter_apply(const cm2_filter *f, const double *d_in, double 
     CM2_LAUNCH_OK();
     return 0;
 }
-
-extern "C" const uint32_t *cm2_tiles_index(const cm2_tiles *t);     // cm2_tiles.hip
-extern "C" int64_t cm2_tiles_nt(const cm2_tiles *t);
-extern "C" int64_t cm2_tiles_nvalid(const cm2_tiles *t);
-extern "C" uint64_t cm2_tiles_plan_id(const cm2_tiles *t);
 
 namespace {
 
@@ -781,17 +776,17 @@ extern "C" int cm2_filter_apply_tiles(cm2_filter *f, const cm2_tiles *tiles, con
 {
     CM2_CHECK(f && tiles && h_done, "cm2_filter_apply_tiles: null argument");
     *h_done = 0;
-    CM2_CHECK(cm2_tiles_nt(tiles) == f->nt, "filter has %lld samples, tile plan %lld",
-              (long long)f->nt, (long long)cm2_tiles_nt(tiles));
+    CM2_CHECK(tiles->nt == f->nt, "filter has %lld samples, tile plan %lld",
+              (long long)f->nt, (long long)tiles->nt);
     hipStream_t st = as_stream(stream);
-    const uint32_t *d_idx = cm2_tiles_index(tiles);
+    const uint32_t *d_idx = tiles->d_tb_dst;
     // the lists belong to ONE tile plan: keyed on its id, not on a device address that a later
     // plan could be given again by the allocator
-    const uint64_t plan_id = cm2_tiles_plan_id(tiles);
+    const uint64_t plan_id = tiles->plan_id;
     if (f->win_plan != plan_id)
         if (int rc = filter_windows_build(f, d_idx, plan_id, st)) return rc;
     if (!f->win_ok) return 0;                         // caller falls back to the time order
-    const int64_t nvalid = cm2_tiles_nvalid(tiles);
+    const int64_t nvalid = tiles->nvalid;
     CM2_CHECK(nvalid == 0 || (d_in_tb && d_out_tb && d_in_tb != d_out_tb),
               "cm2_filter_apply_tiles: null or aliased vectors");
     if (f->win_memset && nvalid) CM2_HIP(hipMemsetAsync(d_out_tb, 0, sizeof(double) * nvalid, st));

@@ -20,8 +20,8 @@
 // Algorithmic traffic 16 B/sample (read v, write y); the rocFFT route moves
 // ~7x that through HBM (pack, 2 FFTs, spectrum multiply, unpack) -- see DESIGN.md.
 #include "cm2_overlap_save.h"
-
-#include <rocfft/rocfft.h>
+#include "cm2_rocfft.h"
+#include "cm2_tiles.h"
 
 #include <cstdlib>
 #include <mutex>
@@ -35,42 +35,70 @@ struct DirTile {
     int32_t len, blk;
 };
 
-struct cm2_noise {
+// The state of a Toeplitz operator in three parts, one per route of application, each the owner of what it
+// holds: reset() (and the destructor) frees it.  An operator fills the part of its method at creation.
+
+// DIRECT, LDS-tiled: the work list of k_toeplitz_direct_tiled (empty for a band too long for the LDS, which
+// the plain loop serves)
+struct DirRoute : NoCopy {
+    size_t lds = 0;                  // dynamic LDS of the tiled kernel for this band
+    DirTile *d_tiles = nullptr;
+    int64_t ntiles = 0;
+    ~DirRoute() { reset(); }
+    void reset()
+    {
+        dev_release(d_tiles);
+        ntiles = 0;
+        lds = 0;
+    }
+};
+
+// FFT: overlap-save through rocFFT, all segments in one batch
+struct FftRoute : NoCopy {
+    int64_t nseg = 0, nfreq = 0;
+    int64_t *d_seg = nullptr;    // [nseg*4]: out_start, out_len, blk_lo, blk_hi
+    int32_t *d_seg_blk = nullptr;
+    double *d_X = nullptr;       // [nseg][L]
+    double2 *d_F = nullptr;      // [nseg][L/2+1]
+    double *d_H = nullptr;       // [nb][L/2+1] real spectra, 1/L folded in
+    RealFft fft;                 // forward and inverse of nseg segments, one info, one work buffer
+    ~FftRoute() { reset(); }
+    void reset()
+    {
+        dev_release(d_seg, d_seg_blk, d_X, d_F, d_H);
+        fft.reset();
+        nseg = nfreq = 0;
+    }
+};
+
+// FUSED: the register-FFT overlap-save kernel (cm2_overlap_save.hip).  Set at creation for method
+// CM2_TOEPLITZ_FUSED; for AUTO -> DIRECT / FFT operators built on first application on a tile order.
+struct FusedRoute : NoCopy {
+    FusedOS *os = nullptr;
+    ~FusedRoute() { reset(); }
+    void reset()
+    {
+        if (os) fused_os_destroy(os);
+        os = nullptr;
+    }
+};
+
+struct cm2_noise : NoCopy {
     int64_t nt = 0, nb = 0, lambda = 0;
     int method = 0;
     bool equal_sizes = true;
     int64_t bsize = 0;
     int64_t *d_off = nullptr;    // [nb+1] block offsets
     double *d_t = nullptr;       // [nb] diagonal values  | [nb*lambda] bands
-    // overlap-save state
-    int64_t L = 0, hop = 0, halo = 0, nseg = 0, nfreq = 0;
-    int64_t *d_seg = nullptr;    // [nseg*4]: out_start, out_len, blk_lo, blk_hi
-    int32_t *d_seg_blk = nullptr;
-    double *d_X = nullptr;       // [nseg][L]
-    double2 *d_F = nullptr;      // [nseg][L/2+1]
-    double *d_H = nullptr;       // [nb][L/2+1] real spectra, 1/L folded in
-    rocfft_plan fwd = nullptr, inv = nullptr;
-    rocfft_execution_info info = nullptr;
-    void *d_fftwork = nullptr;
-    size_t fftwork_bytes = 0;
-    cm2::FusedOS *fused = nullptr;   // method CM2_TOEPLITZ_FUSED; for AUTO -> DIRECT / FFT operators
-                                     // built on first application on a tile order
-    DirTile *d_dirtiles = nullptr;   // work list of the tiled direct kernel
-    int64_t ndirtiles = 0;
+    int64_t L = 0, hop = 0, halo = 0;   // overlap-save geometry (FFT and FUSED)
+    DirRoute dir;
+    FftRoute fft;
+    FusedRoute fused;
     bool auto_method = false;        // the caller left the choice to the library
     std::vector<int64_t> h_off;      // block offsets (host)
-    std::mutex mu;                   // lazy creation of `fused`
+    std::mutex mu;                   // lazy creation of `fused.os`
+    ~cm2_noise() { dev_release(d_off, d_t); }
 };
-
-#define CM2_FFT(call)                                                                  \
-    do {                                                                               \
-        rocfft_status s__ = (call);                                                    \
-        if (s__ != rocfft_status_success) {                                            \
-            cm2::set_error("%s failed: rocfft_status %d (%s:%d)", #call, (int)s__,     \
-                           __FILE__, __LINE__);                                        \
-            return 3;                                                                  \
-        }                                                                              \
-    } while (0)
 
 __device__ __forceinline__ int find_block(const int64_t *__restrict__ off, int nb, int64_t k,
                                           bool equal, int64_t bsize)
@@ -232,10 +260,12 @@ __global__ __launch_bounds__(256) void k_unpack(int64_t L, int64_t halo,
 }
 
 // ------------------------------------------------------------------ C ABI ------
-static int noise_common(cm2_noise *n, const int64_t *h_sizes, int64_t nb,
-                        std::vector<int64_t> &off)
+// block offsets on the host and the device, the values (diagonal entries or bands) on the device
+static int noise_common(cm2_noise *n, const double *h_vals, int64_t per_block, const int64_t *h_sizes,
+                        int64_t nb)
 {
     CM2_CHECK(nb >= 1, "noise operator needs at least one block (nblocks=%lld)", (long long)nb);
+    std::vector<int64_t> &off = n->h_off;
     off.assign(nb + 1, 0);
     n->equal_sizes = true;
     for (int64_t b = 0; b < nb; ++b) {
@@ -249,37 +279,8 @@ static int noise_common(cm2_noise *n, const int64_t *h_sizes, int64_t nb,
     n->bsize = h_sizes[0];
     CM2_HIP(cm2::dev_malloc(&n->d_off, sizeof(int64_t) * (nb + 1)));
     CM2_HIP(cm2::upload(n->d_off, off.data(), sizeof(int64_t) * (nb + 1), nullptr));
-    return 0;
-}
-
-extern "C" int cm2_noise_destroy(cm2_noise *n)
-{
-    if (!n) return 0;
-    if (n->fused) cm2::fused_os_destroy(n->fused);
-    if (n->fwd) rocfft_plan_destroy(n->fwd);
-    if (n->inv) rocfft_plan_destroy(n->inv);
-    if (n->info) rocfft_execution_info_destroy(n->info);
-    void *ptrs[] = {n->d_off, n->d_t, n->d_seg, n->d_seg_blk, n->d_X, n->d_F, n->d_H, n->d_fftwork,
-                    n->d_dirtiles};
-    for (void *q : ptrs)
-        if (q) (void)cm2::dev_free(q);
-    delete n;
-    return 0;
-}
-
-extern "C" int cm2_noise_create_diag(cm2_noise **out, const double *h_t, const int64_t *h_sizes,
-                                     int64_t nblocks)
-{
-    CM2_CHECK(out && h_t && h_sizes, "cm2_noise_create_diag: NULL argument");
-    *out = nullptr;
-    cm2_noise *n = new cm2_noise();
-    std::vector<int64_t> off;
-    if (int rc = noise_common(n, h_sizes, nblocks, off)) { cm2_noise_destroy(n); return rc; }
-    n->lambda = 0;
-    n->method = 0;
-    CM2_HIP(cm2::dev_malloc(&n->d_t, sizeof(double) * nblocks));
-    CM2_HIP(cm2::upload(n->d_t, h_t, sizeof(double) * nblocks, nullptr));
-    *out = n;
+    CM2_HIP(cm2::dev_malloc(&n->d_t, sizeof(double) * nb * per_block));
+    CM2_HIP(cm2::upload(n->d_t, h_vals, sizeof(double) * nb * per_block, nullptr));
     return 0;
 }
 
@@ -298,53 +299,46 @@ static int64_t pick_fft_length(int64_t halo, int64_t max_block)
     return L;
 }
 
-extern "C" int cm2_noise_create_toeplitz(cm2_noise **out, const double *h_bands, int64_t lambda,
-                                         const int64_t *h_sizes, int64_t nblocks, int method,
-                                         void *stream_)
+// a band too long for the LDS of the tiled direct kernel (or an empty TOD) takes the plain loop
+static bool dir_plain_loop(size_t lds, int64_t nt) { return lds > 150 * 1024 || nt == 0; }
+
+// DIRECT: the work list of the tiled kernel, kDirTile outputs of one block per workgroup
+static int dir_build(cm2_noise *n)
 {
-    CM2_CHECK(out && h_bands && h_sizes, "cm2_noise_create_toeplitz: NULL argument");
-    CM2_CHECK(lambda >= 1, "cm2_noise_create_toeplitz: band length lambda=%lld < 1", (long long)lambda);
-    CM2_CHECK(method >= 0 && method <= 3, "cm2_noise_create_toeplitz: bad method %d", method);
-    *out = nullptr;
-    hipStream_t stream = as_stream(stream_);
-    cm2_noise *n = new cm2_noise();
-    std::vector<int64_t> off;
-    if (int rc = noise_common(n, h_sizes, nblocks, off)) { cm2_noise_destroy(n); return rc; }
-    n->lambda = lambda;
-    n->h_off = off;
-    n->auto_method = (method == CM2_TOEPLITZ_AUTO);
-    if (method == CM2_TOEPLITZ_AUTO)
-        method = (lambda <= 32) ? CM2_TOEPLITZ_DIRECT
-                                : (cm2::fused_os_supported(lambda) ? CM2_TOEPLITZ_FUSED
-                                                                   : CM2_TOEPLITZ_FFT);
-    n->method = method;
-    CM2_HIP(cm2::dev_malloc(&n->d_t, sizeof(double) * nblocks * lambda));
-    CM2_HIP(cm2::upload(n->d_t, h_bands, sizeof(double) * nblocks * lambda, nullptr));
-    if (method == CM2_TOEPLITZ_DIRECT) {
-        *out = n;
-        return 0;
-    }
-    if (method == CM2_TOEPLITZ_FUSED) {
-        if (int rc = cm2::fused_os_create(&n->fused, n->d_t, lambda, off, stream)) {
-            cm2_noise_destroy(n);
-            return rc;
+    DirRoute &d = n->dir;
+    d.lds = sizeof(double) * (size_t)(kDirTile + 2 * (n->lambda - 1));
+    if (dir_plain_loop(d.lds, n->nt)) return 0;
+    const std::vector<int64_t> &off = n->h_off;
+    std::vector<DirTile> tl;
+    for (int64_t b = 0; b < n->nb; ++b)
+        for (int64_t s0 = off[(size_t)b]; s0 < off[(size_t)b + 1]; s0 += kDirTile) {
+            DirTile t;
+            t.start = s0;
+            t.len = (int32_t)(off[(size_t)b + 1] - s0 < kDirTile ? off[(size_t)b + 1] - s0 : kDirTile);
+            t.blk = (int32_t)b;
+            tl.push_back(t);
         }
-        n->L = cm2::fused_os_length(n->fused);
-        n->halo = lambda - 1;
-        n->hop = n->L - 2 * n->halo;
-        *out = n;
-        return 0;
-    }
-    // ---- overlap-save plan (rocFFT) ----
+    CM2_HIP(cm2::dev_malloc(&d.d_tiles, sizeof(DirTile) * tl.size()));
+    CM2_HIP(cm2::upload(d.d_tiles, tl.data(), sizeof(DirTile) * tl.size(), nullptr));
+    d.ntiles = (int64_t)tl.size();
+    return 0;
+}
+
+// FFT: segments, spectra of the bands and the rocFFT plans
+static int fft_build(cm2_noise *n, hipStream_t stream)
+{
+    FftRoute &f = n->fft;
+    const std::vector<int64_t> &off = n->h_off;
     int64_t max_block = 0;
-    for (int64_t b = 0; b < nblocks; ++b) max_block = h_sizes[b] > max_block ? h_sizes[b] : max_block;
-    n->halo = lambda - 1;
+    for (int64_t b = 0; b < n->nb; ++b)
+        max_block = off[b + 1] - off[b] > max_block ? off[b + 1] - off[b] : max_block;
+    n->halo = n->lambda - 1;
     n->L = pick_fft_length(n->halo, max_block);
     n->hop = n->L - 2 * n->halo;
-    n->nfreq = n->L / 2 + 1;
+    f.nfreq = n->L / 2 + 1;
     std::vector<int64_t> seg;
     std::vector<int32_t> seg_blk;
-    for (int64_t b = 0; b < nblocks; ++b) {
+    for (int64_t b = 0; b < n->nb; ++b) {
         for (int64_t s0 = off[b]; s0 < off[b + 1]; s0 += n->hop) {
             const int64_t len = (off[b + 1] - s0 < n->hop) ? off[b + 1] - s0 : n->hop;
             seg.push_back(s0);
@@ -354,43 +348,84 @@ extern "C" int cm2_noise_create_toeplitz(cm2_noise **out, const double *h_bands,
             seg_blk.push_back((int32_t)b);
         }
     }
-    n->nseg = (int64_t)seg_blk.size();
-    CM2_CHECK(n->nseg < 65536LL * 32768LL, "too many FFT segments (%lld)", (long long)n->nseg);
-    CM2_HIP(cm2::dev_malloc(&n->d_seg, sizeof(int64_t) * seg.size()));
-    CM2_HIP(cm2::dev_malloc(&n->d_seg_blk, sizeof(int32_t) * seg_blk.size()));
-    CM2_HIP(cm2::upload(n->d_seg, seg.data(), sizeof(int64_t) * seg.size(), nullptr));
-    CM2_HIP(cm2::upload(n->d_seg_blk, seg_blk.data(), sizeof(int32_t) * seg_blk.size(), nullptr));
-    CM2_HIP(cm2::dev_malloc(&n->d_X, sizeof(double) * n->nseg * n->L));
-    CM2_HIP(cm2::dev_malloc(&n->d_F, sizeof(double2) * n->nseg * n->nfreq));
-    CM2_HIP(cm2::dev_malloc(&n->d_H, sizeof(double) * nblocks * n->nfreq));
-    k_spectrum<<<grid_for(nblocks * n->nfreq), kBlock, 0, stream>>>((int)nblocks, lambda, n->L,
-                                                                   n->nfreq, n->d_t, n->d_H);
+    f.nseg = (int64_t)seg_blk.size();
+    CM2_CHECK(f.nseg < 65536LL * 32768LL, "too many FFT segments (%lld)", (long long)f.nseg);
+    CM2_HIP(cm2::dev_malloc(&f.d_seg, sizeof(int64_t) * seg.size()));
+    CM2_HIP(cm2::dev_malloc(&f.d_seg_blk, sizeof(int32_t) * seg_blk.size()));
+    CM2_HIP(cm2::upload(f.d_seg, seg.data(), sizeof(int64_t) * seg.size(), nullptr));
+    CM2_HIP(cm2::upload(f.d_seg_blk, seg_blk.data(), sizeof(int32_t) * seg_blk.size(), nullptr));
+    CM2_HIP(cm2::dev_malloc(&f.d_X, sizeof(double) * f.nseg * n->L));
+    CM2_HIP(cm2::dev_malloc(&f.d_F, sizeof(double2) * f.nseg * f.nfreq));
+    CM2_HIP(cm2::dev_malloc(&f.d_H, sizeof(double) * n->nb * f.nfreq));
+    k_spectrum<<<grid_for(n->nb * f.nfreq), kBlock, 0, stream>>>((int)n->nb, n->lambda, n->L, f.nfreq,
+                                                                 n->d_t, f.d_H);
     CM2_LAUNCH_OK();
-
-    static bool rocfft_ready = false;
-    if (!rocfft_ready) {
-        CM2_FFT(rocfft_setup());
-        rocfft_ready = true;
-    }
-    const size_t lengths[1] = {(size_t)n->L};
-    CM2_FFT(rocfft_plan_create(&n->fwd, rocfft_placement_notinplace,
-                               rocfft_transform_type_real_forward, rocfft_precision_double, 1,
-                               lengths, (size_t)n->nseg, nullptr));
-    CM2_FFT(rocfft_plan_create(&n->inv, rocfft_placement_notinplace,
-                               rocfft_transform_type_real_inverse, rocfft_precision_double, 1,
-                               lengths, (size_t)n->nseg, nullptr));
-    size_t w1 = 0, w2 = 0;
-    CM2_FFT(rocfft_plan_get_work_buffer_size(n->fwd, &w1));
-    CM2_FFT(rocfft_plan_get_work_buffer_size(n->inv, &w2));
-    n->fftwork_bytes = w1 > w2 ? w1 : w2;
-    CM2_FFT(rocfft_execution_info_create(&n->info));
-    if (n->fftwork_bytes) {
-        CM2_HIP(cm2::dev_malloc(&n->d_fftwork, n->fftwork_bytes));
-        CM2_FFT(rocfft_execution_info_set_work_buffer(n->info, n->d_fftwork, n->fftwork_bytes));
-    }
+    if (int rc = f.fft.plan(n->L, f.nseg, true)) return rc;
+    if (int rc = f.fft.bind()) return rc;
     CM2_HIP(hipStreamSynchronize(stream));
+    return 0;
+}
+
+// The one build path of both kinds of operator (lambda = 0: constant diagonal).  It may return from any
+// line: the caller destroys the operator, which frees what was built so far.
+static int noise_build(cm2_noise *n, const double *h_vals, int64_t lambda, const int64_t *h_sizes,
+                       int64_t nblocks, int method, hipStream_t stream)
+{
+    if (int rc = noise_common(n, h_vals, lambda ? lambda : 1, h_sizes, nblocks)) return rc;
+    n->lambda = lambda;
+    if (lambda == 0) return 0;
+    n->auto_method = (method == CM2_TOEPLITZ_AUTO);
+    if (method == CM2_TOEPLITZ_AUTO)
+        method = (lambda <= 32) ? CM2_TOEPLITZ_DIRECT
+                                : (cm2::fused_os_supported(lambda) ? CM2_TOEPLITZ_FUSED
+                                                                   : CM2_TOEPLITZ_FFT);
+    n->method = method;
+    if (method == CM2_TOEPLITZ_DIRECT) return dir_build(n);
+    if (method == CM2_TOEPLITZ_FFT) return fft_build(n, stream);
+    if (int rc = cm2::fused_os_create(&n->fused.os, n->d_t, lambda, n->h_off, stream)) return rc;
+    n->L = cm2::fused_os_length(n->fused.os);
+    n->halo = lambda - 1;
+    n->hop = n->L - 2 * n->halo;
+    return 0;
+}
+
+// new, build, and on failure destroy: nothing between `new` and the hand-over to *out returns early
+static int noise_create(cm2_noise **out, const double *h_vals, int64_t lambda, const int64_t *h_sizes,
+                        int64_t nblocks, int method, hipStream_t stream)
+{
+    cm2_noise *n = new cm2_noise();
+    const int rc = noise_build(n, h_vals, lambda, h_sizes, nblocks, method, stream);
+    if (rc) {
+        cm2_noise_destroy(n);
+        return rc;
+    }
     *out = n;
     return 0;
+}
+
+extern "C" int cm2_noise_destroy(cm2_noise *n)
+{
+    delete n;                // every part frees what it owns
+    return 0;
+}
+
+extern "C" int cm2_noise_create_diag(cm2_noise **out, const double *h_t, const int64_t *h_sizes,
+                                     int64_t nblocks)
+{
+    CM2_CHECK(out && h_t && h_sizes, "cm2_noise_create_diag: NULL argument");
+    *out = nullptr;
+    return noise_create(out, h_t, 0, h_sizes, nblocks, 0, nullptr);
+}
+
+extern "C" int cm2_noise_create_toeplitz(cm2_noise **out, const double *h_bands, int64_t lambda,
+                                         const int64_t *h_sizes, int64_t nblocks, int method,
+                                         void *stream_)
+{
+    CM2_CHECK(out && h_bands && h_sizes, "cm2_noise_create_toeplitz: NULL argument");
+    CM2_CHECK(lambda >= 1, "cm2_noise_create_toeplitz: band length lambda=%lld < 1", (long long)lambda);
+    CM2_CHECK(method >= 0 && method <= 3, "cm2_noise_create_toeplitz: bad method %d", method);
+    *out = nullptr;
+    return noise_create(out, h_bands, lambda, h_sizes, nblocks, method, as_stream(stream_));
 }
 
 extern "C" int cm2_noise_info(const cm2_noise *n, int64_t *h_info)
@@ -407,7 +442,7 @@ extern "C" int cm2_noise_tile_kernel_info(const cm2_noise *n, int64_t *h_info, d
 {
     CM2_CHECK(n && h_info && h_bytes_per_sample, "cm2_noise_tile_kernel_info: NULL argument");
     int kernel[2] = {0, 0};
-    *h_bytes_per_sample = cm2::fused_os_tile_info(n->fused, kernel);
+    *h_bytes_per_sample = cm2::fused_os_tile_info(n->fused.os, kernel);
     h_info[0] = kernel[0];
     h_info[1] = kernel[1];
     h_info[2] = 512 * (int64_t)kernel[0];                 // window samples
@@ -437,65 +472,49 @@ extern "C" int cm2_noise_apply(cm2_noise *n, const double *d_v, double *d_out, v
         return 0;
     }
     if (n->method == CM2_TOEPLITZ_DIRECT) {
-        const size_t lds = sizeof(double) * (size_t)(kDirTile + 2 * (n->lambda - 1));
-        if (lds > 150 * 1024 || n->nt == 0) {           // very long bands: the plain loop
+        const DirRoute &d = n->dir;
+        if (dir_plain_loop(d.lds, n->nt)) {             // very long bands: the plain loop
             k_toeplitz_direct<<<grid_for(n->nt), kBlock, 0, stream>>>(
                 n->nt, (int)n->nb, n->equal_sizes, n->bsize, n->lambda, n->d_off, n->d_t, d_v, d_out);
             CM2_LAUNCH_OK();
             return 0;
         }
-        if (!n->d_dirtiles) {
-            std::vector<DirTile> tl;
-            for (int64_t b = 0; b < n->nb; ++b)
-                for (int64_t s0 = n->h_off[(size_t)b]; s0 < n->h_off[(size_t)b + 1]; s0 += kDirTile) {
-                    DirTile d;
-                    d.start = s0;
-                    d.len = (int32_t)(n->h_off[(size_t)b + 1] - s0 < kDirTile ? n->h_off[(size_t)b + 1] - s0
-                                                                              : kDirTile);
-                    d.blk = (int32_t)b;
-                    tl.push_back(d);
-                }
-            n->ndirtiles = (int64_t)tl.size();
-            CM2_HIP(cm2::dev_malloc(&n->d_dirtiles, sizeof(DirTile) * (tl.size() ? tl.size() : 1)));
-            if (!tl.empty())
-                CM2_HIP(cm2::upload(n->d_dirtiles, tl.data(), sizeof(DirTile) * tl.size(), nullptr));
-            if (lds > 64 * 1024)
-                CM2_HIP(hipFuncSetAttribute((const void *)k_toeplitz_direct_tiled,
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        if (d.lds > 64 * 1024) {
+            static size_t granted[64] = {0};
+            CM2_HIP(ensure_dynamic_lds((const void *)k_toeplitz_direct_tiled, d.lds, granted));
         }
-        if (n->ndirtiles)
-            k_toeplitz_direct_tiled<<<(unsigned)n->ndirtiles, kDirT, lds, stream>>>(
-                n->d_dirtiles, n->lambda, n->d_off, n->d_t, d_v, d_out);
+        if (d.ntiles)
+            k_toeplitz_direct_tiled<<<(unsigned)d.ntiles, kDirT, d.lds, stream>>>(
+                d.d_tiles, n->lambda, n->d_off, n->d_t, d_v, d_out);
         CM2_LAUNCH_OK();
         return 0;
     }
-    if (n->method == CM2_TOEPLITZ_FUSED) return cm2::fused_os_apply(n->fused, d_v, d_out, stream);
+    if (n->method == CM2_TOEPLITZ_FUSED) return cm2::fused_os_apply(n->fused.os, d_v, d_out, stream);
     // overlap-save: pack -> R2C -> spectrum multiply -> C2R -> unpack
+    FftRoute &f = n->fft;
     const int gx_L = (int)((n->L + kBlock * 4 - 1) / (kBlock * 4));
     const int64_t per_launch = 65535;             // gridDim.y limit
-    for (int64_t s0 = 0; s0 < n->nseg; s0 += per_launch) {
-        const int ny = (int)((n->nseg - s0 < per_launch) ? n->nseg - s0 : per_launch);
-        k_pack<<<dim3(gx_L, ny), kBlock, 0, stream>>>(n->L, n->halo, n->d_seg + 4 * s0, d_v,
-                                                      n->d_X + s0 * n->L);
+    for (int64_t s0 = 0; s0 < f.nseg; s0 += per_launch) {
+        const int ny = (int)((f.nseg - s0 < per_launch) ? f.nseg - s0 : per_launch);
+        k_pack<<<dim3(gx_L, ny), kBlock, 0, stream>>>(n->L, n->halo, f.d_seg + 4 * s0, d_v,
+                                                      f.d_X + s0 * n->L);
         CM2_LAUNCH_OK();
     }
-    CM2_FFT(rocfft_execution_info_set_stream(n->info, stream));
-    void *in1[1] = {n->d_X}, *out1[1] = {n->d_F};
-    CM2_FFT(rocfft_execute(n->fwd, in1, out1, n->info));
-    const int gx_F = (int)((n->nfreq + kBlock * 4 - 1) / (kBlock * 4));
-    for (int64_t s0 = 0; s0 < n->nseg; s0 += per_launch) {
-        const int ny = (int)((n->nseg - s0 < per_launch) ? n->nseg - s0 : per_launch);
-        k_spec_mul<<<dim3(gx_F, ny), kBlock, 0, stream>>>(n->nfreq, n->d_seg_blk + s0, n->d_H,
-                                                          n->d_F + s0 * n->nfreq);
+    if (int rc = f.fft.set_stream(stream)) return rc;
+    if (int rc = f.fft.forward(f.d_X, f.d_F)) return rc;
+    const int gx_F = (int)((f.nfreq + kBlock * 4 - 1) / (kBlock * 4));
+    for (int64_t s0 = 0; s0 < f.nseg; s0 += per_launch) {
+        const int ny = (int)((f.nseg - s0 < per_launch) ? f.nseg - s0 : per_launch);
+        k_spec_mul<<<dim3(gx_F, ny), kBlock, 0, stream>>>(f.nfreq, f.d_seg_blk + s0, f.d_H,
+                                                          f.d_F + s0 * f.nfreq);
         CM2_LAUNCH_OK();
     }
-    void *in2[1] = {n->d_F}, *out2[1] = {n->d_X};
-    CM2_FFT(rocfft_execute(n->inv, in2, out2, n->info));
+    if (int rc = f.fft.inverse(f.d_F, f.d_X)) return rc;
     const int gx_O = (int)((n->hop + kBlock * 4 - 1) / (kBlock * 4));
-    for (int64_t s0 = 0; s0 < n->nseg; s0 += per_launch) {
-        const int ny = (int)((n->nseg - s0 < per_launch) ? n->nseg - s0 : per_launch);
-        k_unpack<<<dim3(gx_O, ny), kBlock, 0, stream>>>(n->L, n->halo, n->d_seg + 4 * s0,
-                                                        n->d_X + s0 * n->L, d_out);
+    for (int64_t s0 = 0; s0 < f.nseg; s0 += per_launch) {
+        const int ny = (int)((f.nseg - s0 < per_launch) ? f.nseg - s0 : per_launch);
+        k_unpack<<<dim3(gx_O, ny), kBlock, 0, stream>>>(n->L, n->halo, f.d_seg + 4 * s0,
+                                                        f.d_X + s0 * n->L, d_out);
         CM2_LAUNCH_OK();
     }
     return 0;
@@ -504,41 +523,33 @@ extern "C" int cm2_noise_apply(cm2_noise *n, const double *d_v, double *d_out, v
 // N^-1 applied to a TOD held in the tile-bucketed order of cm2_tiles (input and output):
 // the overlap-save kernel gathers its segment through the tile index and scatters the
 // result back the same way, so no time-ordered copy of the TOD is ever written.
-struct cm2_tiles;
-extern "C" const uint32_t *cm2_tiles_index(const cm2_tiles *t);
-extern "C" int64_t cm2_tiles_nt(const cm2_tiles *t);
-extern "C" uint64_t cm2_tiles_plan_id(const cm2_tiles *t);
-extern "C" int64_t cm2_tiles_ntiles(const cm2_tiles *t);
-extern "C" int64_t cm2_tiles_nvalid(const cm2_tiles *t);
-extern "C" const int64_t *cm2_tiles_offsets(const cm2_tiles *t);
-
 static int noise_tiles_ready(cm2_noise *n, const cm2_tiles *tiles, const char *who, void *stream_)
 {
     if (n->auto_method && n->method != CM2_TOEPLITZ_FUSED && n->lambda > 0 && cm2::fused_os_supported(n->lambda)) {
         // the method was left to the library and resolved to the direct sum (short band) for
-        // the time order; on a tile order the fused overlap-save kernel is the fast one.  n->fused is
+        // the time order; on a tile order the fused overlap-save kernel is the fast one.  n->fused.os is
         // only read and written under the operator's lock on this path (application calls of several
         // host threads may meet here; the operators built with CM2_TOEPLITZ_FUSED set it at creation).
         std::lock_guard<std::mutex> lock(n->mu);
-        if (!n->fused)
-            if (int rc = cm2::fused_os_create(&n->fused, n->d_t, n->lambda, n->h_off, as_stream(stream_)))
+        if (!n->fused.os)
+            if (int rc = cm2::fused_os_create(&n->fused.os, n->d_t, n->lambda, n->h_off, as_stream(stream_)))
                 return rc;
     }
-    CM2_CHECK(n->fused && (n->method == CM2_TOEPLITZ_FUSED || n->auto_method),
+    CM2_CHECK(n->fused.os && (n->method == CM2_TOEPLITZ_FUSED || n->auto_method),
               "%s needs a Toeplitz operator built with CM2_TOEPLITZ_FUSED or CM2_TOEPLITZ_AUTO", who);
-    CM2_CHECK(cm2_tiles_nt(tiles) == n->nt, "noise operator has %lld samples, tile plan %lld",
-              (long long)n->nt, (long long)cm2_tiles_nt(tiles));
+    CM2_CHECK(tiles->nt == n->nt, "noise operator has %lld samples, tile plan %lld",
+              (long long)n->nt, (long long)tiles->nt);
     return 0;
 }
 
 static cm2::OsPlanView plan_view(const cm2_tiles *tiles)
 {
     cm2::OsPlanView pv;
-    pv.d_idx = cm2_tiles_index(tiles);
-    pv.d_tile_off = cm2_tiles_offsets(tiles);
-    pv.plan_id = cm2_tiles_plan_id(tiles);
-    pv.ntiles = cm2_tiles_ntiles(tiles);
-    pv.nvalid = cm2_tiles_nvalid(tiles);
+    pv.d_idx = tiles->d_tb_dst;
+    pv.d_tile_off = tiles->d_tile_off;
+    pv.plan_id = tiles->plan_id;
+    pv.ntiles = tiles->ntiles;
+    pv.nvalid = tiles->nvalid;
     return pv;
 }
 
@@ -546,7 +557,7 @@ extern "C" int cm2_noise_prepare_tiles(cm2_noise *n, const cm2_tiles *tiles, voi
 {
     CM2_CHECK(n && tiles, "cm2_noise_prepare_tiles: NULL argument");
     if (int rc = noise_tiles_ready(n, tiles, "cm2_noise_prepare_tiles", stream_)) return rc;
-    return cm2::fused_os_prepare_indexed(n->fused, plan_view(tiles), as_stream(stream_));
+    return cm2::fused_os_prepare_indexed(n->fused.os, plan_view(tiles), as_stream(stream_));
 }
 
 extern "C" int cm2_noise_apply_tiles(cm2_noise *n, const cm2_tiles *tiles, const double *d_in_tb,
@@ -555,16 +566,13 @@ extern "C" int cm2_noise_apply_tiles(cm2_noise *n, const cm2_tiles *tiles, const
     CM2_CHECK(n && tiles && d_in_tb && d_out_tb, "cm2_noise_apply_tiles: NULL argument");
     CM2_CHECK(d_in_tb != d_out_tb, "cm2_noise_apply_tiles: in-place application is not supported");
     if (int rc = noise_tiles_ready(n, tiles, "cm2_noise_apply_tiles", stream_)) return rc;
-    return cm2::fused_os_apply_indexed(n->fused, plan_view(tiles), d_in_tb, d_out_tb, as_stream(stream_));
+    return cm2::fused_os_apply_indexed(n->fused.os, plan_view(tiles), d_in_tb, d_out_tb, as_stream(stream_));
 }
 
 // One call for the whole tile-order chain y = P^T N^-1 P x (SURVEY 8b's fused cm2_PtNP_apply):
 // k_P_tiles, the overlap-save kernel on the tile order, the fixed-order (or atomic) P^T -- three
 // launches on `stream`, no allocation when the plan was prepared (cm2_tiles_prepare_pt) and the
 // operator has run once on this plan.  d_tb1 / d_tb2: scratch of >= (valid samples) doubles each.
-extern "C" int cm2_P_tiles_apply(const cm2_tiles *t, const double *d_x, double *d_tod_tb, void *stream);
-extern "C" int cm2_Pt_tiles_apply(const cm2_tiles *t, const double *d_tod_tb, double *d_out, void *stream);
-
 extern "C" int cm2_PtNP_tiles_apply(const cm2_tiles *tiles, cm2_noise *n, const double *d_x,
                                     double *d_y, double *d_tb1, double *d_tb2, void *stream)
 {

@@ -20,9 +20,7 @@
 // workspace cap; the last batch is padded with zero segments), so a segment's rocFFT transform is the same
 // whichever segments share its batch, and the per-bin sums run in segment order across batch boundaries:
 // a block estimated alone gives the bits of the same block estimated inside a group.
-#include "cm2_common.h"
-
-#include <rocfft/rocfft.h>
+#include "cm2_rocfft.h"
 
 #include <cmath>
 #include <vector>
@@ -30,18 +28,6 @@
 using namespace cm2;
 
 namespace {
-
-// rocFFT reports no out-of-memory status of its own: every failure of the library is CM2_ERR_HIP (only the
-// allocations this unit makes itself, through CM2_HIP, can give CM2_ERR_OUT_OF_MEMORY)
-#define CM2_ROCFFT(call)                                                               \
-    do {                                                                               \
-        rocfft_status s__ = (call);                                                    \
-        if (s__ != rocfft_status_success) {                                            \
-            cm2::set_error("%s failed: rocfft_status %d (%s:%d)", #call, (int)s__,     \
-                           __FILE__, __LINE__);                                        \
-            return CM2_ERR_HIP;                                                        \
-        }                                                                              \
-    } while (0)
 
 constexpr int64_t kMinL = 256, kMaxL = 65536;
 constexpr int64_t kBatchSamples = int64_t(1) << 24;     // segments per batch * L, at most (128 MB of input)
@@ -188,44 +174,27 @@ struct cm2_psd {
     double *d_win = nullptr;      // [L] periodic Hann window
     double *d_X = nullptr;        // [batch][L] windowed segments
     double2 *d_F = nullptr;       // [batch][L/2+1] their transforms
-    void *d_fftwork = nullptr;
-    size_t fftwork_bytes = 0;
-    rocfft_plan plan = nullptr;
-    rocfft_execution_info info = nullptr;
+    cm2::RealFft fft;             // forward transform of `batch` segments
+    ~cm2_psd() { dev_release(d_win, d_X, d_F); }
 };
 
 extern "C" int cm2_psd_destroy(cm2_psd *p)
 {
-    if (!p) return 0;
-    if (p->plan) rocfft_plan_destroy(p->plan);
-    if (p->info) rocfft_execution_info_destroy(p->info);
-    void *ptrs[] = {p->d_win, p->d_X, p->d_F, p->d_fftwork};
-    for (void *q : ptrs)
-        if (q) (void)cm2::dev_free(q);
     delete p;
     return 0;
 }
 
 static int psd_build(cm2_psd *p, int64_t max_work_bytes, hipStream_t stream)
 {
-    static std::once_flag once;
-    static rocfft_status setup = rocfft_status_success;
-    std::call_once(once, [] { setup = rocfft_setup(); });
-    CM2_ROCFFT(setup);
     const int64_t L = p->L;
     const int64_t per_seg = (int64_t)(sizeof(double) * L + sizeof(double2) * p->nfreq);
     int64_t batch = kBatchSamples / L;
     if (batch * per_seg > max_work_bytes) batch = max_work_bytes / per_seg;
     if (batch < 1) batch = 1;
     // the rocFFT work buffer counts against the cap too: halve the batch until it fits (or is one segment)
-    const size_t lengths[1] = {(size_t)L};
     for (;;) {
-        CM2_ROCFFT(rocfft_plan_create(&p->plan, rocfft_placement_notinplace, rocfft_transform_type_real_forward,
-                                      rocfft_precision_double, 1, lengths, (size_t)batch, nullptr));
-        CM2_ROCFFT(rocfft_plan_get_work_buffer_size(p->plan, &p->fftwork_bytes));
-        if (batch == 1 || batch * per_seg + (int64_t)p->fftwork_bytes <= max_work_bytes) break;
-        rocfft_plan_destroy(p->plan);
-        p->plan = nullptr;
+        if (int rc = p->fft.plan(L, batch, false)) return rc;
+        if (batch == 1 || batch * per_seg + (int64_t)p->fft.work_bytes <= max_work_bytes) break;
         batch /= 2;
     }
     p->batch = batch;
@@ -240,12 +209,7 @@ static int psd_build(cm2_psd *p, int64_t max_work_bytes, hipStream_t stream)
     CM2_HIP(cm2::upload(p->d_win, w.data(), sizeof(double) * L, stream));
     CM2_HIP(cm2::dev_malloc(&p->d_X, sizeof(double) * L * batch));
     CM2_HIP(cm2::dev_malloc(&p->d_F, sizeof(double2) * p->nfreq * batch));
-    CM2_ROCFFT(rocfft_execution_info_create(&p->info));
-    if (p->fftwork_bytes) {
-        CM2_HIP(cm2::dev_malloc_bytes(&p->d_fftwork, p->fftwork_bytes));
-        CM2_ROCFFT(rocfft_execution_info_set_work_buffer(p->info, p->d_fftwork, p->fftwork_bytes));
-    }
-    return 0;
+    return p->fft.bind();
 }
 
 extern "C" int cm2_psd_create(cm2_psd **out, int64_t nperseg, int detrend, int64_t max_work_bytes, void *stream_)
@@ -274,7 +238,7 @@ extern "C" int cm2_psd_info(const cm2_psd *p, int64_t *h_info)
     h_info[0] = p->L;
     h_info[1] = p->batch;
     h_info[2] = (int64_t)(sizeof(double) * p->L * p->batch + sizeof(double2) * p->nfreq * p->batch +
-                          p->fftwork_bytes);
+                          p->fft.work_bytes);
     return 0;
 }
 
@@ -300,14 +264,13 @@ extern "C" int cm2_psd_welch(cm2_psd *p, const double *d_tod, const int64_t *h_s
     CM2_HIP(cm2::upload(d_off, off.data(), sizeof(int64_t) * (nb + 1), stream));
     CM2_HIP(cm2::upload(d_seg_off, seg_off.data(), sizeof(int64_t) * (nb + 1), stream));
     CM2_HIP(hipMemsetAsync(d_psd, 0, sizeof(double) * nb * nfreq, stream));
-    CM2_ROCFFT(rocfft_execution_info_set_stream(p->info, stream));
+    if (int rc = p->fft.set_stream(stream)) return rc;
     int64_t b_lo = 0;
     for (int64_t first = 0; first < nseg; first += batch) {
         k_psd_pack<<<(unsigned)batch, kBlock, 0, stream>>>(d_tod, d_off, d_seg_off, nb, nseg, first, L, p->detrend,
                                                            p->d_win, p->d_X);
         CM2_LAUNCH_OK();
-        void *in[1] = {p->d_X}, *outp[1] = {p->d_F};
-        CM2_ROCFFT(rocfft_execute(p->plan, in, outp, p->info));
+        if (int rc = p->fft.forward(p->d_X, p->d_F)) return rc;
         // blocks with segments in [first, first + batch)
         while (seg_off[b_lo + 1] <= first) ++b_lo;
         int64_t b_hi = b_lo;

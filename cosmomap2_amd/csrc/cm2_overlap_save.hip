@@ -1087,7 +1087,7 @@ static int os_launch(const FusedOS *f, const OsLists *ls, int64_t nvalid, const 
     if (ls->mode == 1 || ((ls->mode == 2 || ls->mode == 3) && os::table_fits(ls->rmax)))
         return launch[ls->mode - 1][nbytes != 0u](f, ls, d_v, d_out, nbytes, stream);
     set_error("fused overlap-save: run table of %d words per list does not fit the kernel", ls->rmax);
-    return 2;
+    return CM2_ERR_ARGUMENT;
 }
 
 int fused_os_apply(const FusedOS *f, const double *d_v, double *d_out, hipStream_t stream)

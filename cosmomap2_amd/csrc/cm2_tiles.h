@@ -1,5 +1,7 @@
-// cm2_tiles.h -- the tile-bucketed pointing plan shared by cm2_tiles.hip (plan, P, atomic P^T,
-// permutations), cm2_tiles_fixed.hip (fixed-order P^T) and cm2_fx_lists.hip (its list builders)
+// cm2_tiles.h -- the tile-bucketed pointing plan.  Written by cm2_tiles.hip (plan, P, atomic P^T,
+// permutations), cm2_tiles_fixed.hip (fixed-order P^T) and cm2_fx_lists.hip (its list builders); read by
+// the units that work on a TOD in the plan's order: cm2_gaps.hip, cm2_noise.hip and cm2_filter.hip
+// (index, offsets, counts and the plan's id)
 #pragma once
 #include "cm2_pixindex.h"
 #include "cm2_plan_policy.h"
@@ -20,15 +22,6 @@ struct PlanSwitches {
     int pt_slice = 0;            // CM2_PT_SLICE=<samples in [64, 2048]>: fixes the slice length (0: tuned)
     int pt_parts = -1;           // CM2_PT_PARTS: 0 = one workgroup per tile, <samples> fixes the part length (-1: chosen)
     bool pt_fuse = true;         // CM2_PT_FUSE=0 (or no number): hot ranges and part copies in kernels of their own
-};
-
-// frees the device buffers it is given and clears the pointers
-template <typename... P>
-inline void dev_release(P *&...p) { ((p ? (void)dev_free(p) : (void)0, p = nullptr), ...); }
-struct NoCopy {
-    NoCopy() = default;
-    NoCopy(const NoCopy &) = delete;
-    NoCopy &operator=(const NoCopy &) = delete;
 };
 
 // The state of the fixed-order P^T in three parts, each the owner of its device buffers: reset() (and the

@@ -923,12 +923,6 @@ extern "C" int cm2_tiles_set_pt_order(cm2_tiles *t, int fixed)
     return 0;
 }
 
-extern "C" uint64_t cm2_tiles_plan_id(const cm2_tiles *t) { return t ? t->plan_id : 0; }
-extern "C" int64_t cm2_tiles_ntiles(const cm2_tiles *t) { return t ? t->ntiles : 0; }
-extern "C" int64_t cm2_tiles_nvalid(const cm2_tiles *t) { return t ? t->nvalid : 0; }
-// first tile-order address of every tile, [ntiles + 1] on the device (internal: cm2_noise.hip)
-extern "C" const int64_t *cm2_tiles_offsets(const cm2_tiles *t) { return t ? t->d_tile_off : nullptr; }
-
 // Tile indices bounding `ngroups` consecutive groups of tiles whose PIXEL boundaries are the same on
 // every rank of a sharded run (ranks with different hit maps may have cut their tiles differently):
 // group g = tiles [h_tiles[g], h_tiles[g + 1]).  Up to 8 groups are bounded by policy::shared_cuts, the
@@ -1154,8 +1148,3 @@ extern "C" int cm2_tod_tiles_to_time(const cm2_tiles *t, const double *d_tb, dou
     CM2_LAUNCH_OK();
     return 0;
 }
-
-// device address of the time -> tile-order index (nt entries), for kernels that fuse the
-// permutation into their own loads and stores (cm2_noise_apply_tiles)
-extern "C" const uint32_t *cm2_tiles_index(const cm2_tiles *t) { return t ? t->d_tb_dst : nullptr; }
-extern "C" int64_t cm2_tiles_nt(const cm2_tiles *t) { return t ? t->nt : 0; }

@@ -21,6 +21,9 @@ namespace {
 constexpr int kRedBlocks = 1024;            // stage-1 workgroups of every reduction
 constexpr int kGemmBlocks = 128;            // workgroups of the Z^T Z contraction
 typedef double double4_t __attribute__((ext_vector_type(4)));
+// A failed callback of the caller (operator, preconditioner, reduction) is reported under CM2_ERR_HIP.
+// cm2_arnoldi ran its inner_m steps without meeting the stop rule: a result of its own, not one of the CM2_ERR_*
+constexpr int kArnoldiNotConverged = 4;
 }  // namespace
 
 extern "C" int64_t cm2_reduce_work_doubles(void) { return (int64_t)kRedBlocks * 256; }
@@ -204,7 +207,7 @@ static int pcg_run(int64_t n, cm2_apply_fn A, void *A_ctx, cm2_apply_fn M, void 
     auto red_dot = [&](double *d) -> int {
         if (reduce && layout == CM2_LAYOUT_ROWS && reduce(reduce_ctx, d, 1, CM2_REDUCE_SUM, stream_)) {
             set_error("cm2_pcg_sharded: the reduction callback failed");
-            return 1;
+            return CM2_ERR_HIP;
         }
         return 0;
     };
@@ -212,7 +215,7 @@ static int pcg_run(int64_t n, cm2_apply_fn A, void *A_ctx, cm2_apply_fn M, void 
         if (reduce && reduce(reduce_ctx, d, 1, layout == CM2_LAYOUT_ROWS ? CM2_REDUCE_SUM : CM2_REDUCE_MAX,
                              stream_)) {
             set_error("cm2_pcg_sharded: the reduction callback failed");
-            return 1;
+            return CM2_ERR_HIP;
         }
         return 0;
     };
@@ -256,7 +259,7 @@ static int pcg_run(int64_t n, cm2_apply_fn A, void *A_ctx, cm2_apply_fn M, void 
         CM2_HIP(hipMemsetAsync(d_x, 0, sizeof(double) * n, stream));
         CM2_HIP(hipMemcpyAsync(r.p, d_b, sizeof(double) * n, hipMemcpyDeviceToDevice, stream));
     } else {                                               // r = b - A x0
-        if (A(A_ctx, d_x, q.p, stream_)) { set_error("cm2_pcg: the operator callback failed"); return 1; }
+        if (A(A_ctx, d_x, q.p, stream_)) { set_error("cm2_pcg: the operator callback failed"); return CM2_ERR_HIP; }
         CM2_HIP(hipMemcpyAsync(r.p, d_b, sizeof(double) * n, hipMemcpyDeviceToDevice, stream));
         if (int rc = cm2_axpy(n, -1.0, q.p, r.p, stream_)) return rc;
     }
@@ -287,7 +290,7 @@ static int pcg_run(int64_t n, cm2_apply_fn A, void *A_ctx, cm2_apply_fn M, void 
     auto ahead_cheap = [&](int64_t it) -> int {
         const double *zz = r.p;
         if (M) {
-            if (M(M_ctx, r.p, z.p, stream_)) { set_error("cm2_pcg: the preconditioner callback failed"); return 1; }
+            if (M(M_ctx, r.p, z.p, stream_)) { set_error("cm2_pcg: the preconditioner callback failed"); return CM2_ERR_HIP; }
             zz = z.p;
         }
         if (int rc = cm2_dot(n, r.p, zz, rho[cur], work, stream)) return rc;
@@ -297,7 +300,7 @@ static int pcg_run(int64_t n, cm2_apply_fn A, void *A_ctx, cm2_apply_fn M, void 
         return 0;
     };
     auto ahead_matvec = [&]() -> int {
-        if (A(A_ctx, p.p, q.p, stream_)) { set_error("cm2_pcg: the operator callback failed"); return 1; }
+        if (A(A_ctx, p.p, q.p, stream_)) { set_error("cm2_pcg: the operator callback failed"); return CM2_ERR_HIP; }
         if (int rc = cm2_dot(n, p.p, q.p, pq, work, stream)) return rc;
         return red_dot(pq);
     };
@@ -400,7 +403,7 @@ extern "C" int cm2_arnoldi(int64_t n, cm2_apply_fn A, void *A_ctx, const double 
     double *v0 = d_V;
     CM2_HIP(hipMemcpyAsync(v0, d_b, sizeof(double) * n, hipMemcpyDeviceToDevice, stream));
     if (d_x0) {
-        if (A(A_ctx, d_x0, w.p, stream_)) { set_error("cm2_arnoldi: the operator callback failed"); return 1; }
+        if (A(A_ctx, d_x0, w.p, stream_)) { set_error("cm2_arnoldi: the operator callback failed"); return CM2_ERR_HIP; }
         if (int rc = cm2_axpy(n, -1.0, w.p, v0, stream_)) return rc;
     }
     if (int rc = dot(v0, v0)) return rc;
@@ -411,7 +414,7 @@ extern "C" int cm2_arnoldi(int64_t n, cm2_apply_fn A, void *A_ctx, const double 
         double *vnew = (j < inner_m) ? d_V + (int64_t)j * n : w.p;   // the last step's vector is not kept
         if (A(A_ctx, d_V + (int64_t)(j - 1) * n, vnew, stream_)) {
             set_error("cm2_arnoldi: the operator callback failed");
-            return 1;
+            return CM2_ERR_HIP;
         }
         for (int i = 0; i < j; ++i) {
             const double *vi = d_V + (int64_t)i * n;
@@ -432,7 +435,7 @@ extern "C" int cm2_arnoldi(int64_t n, cm2_apply_fn A, void *A_ctx, const double 
         if (fabs(vj * hn) <= tol) return 0;
     }
     set_error("Convergence not achieved within the Arnoldi algorithm");     // deflationlib.py:112
-    return 4;
+    return kArnoldiNotConverged;
 }
 
 // ------------------------------------------------------------- Z^T x ----------

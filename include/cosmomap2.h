@@ -226,7 +226,8 @@ int cm2_noise_create_toeplitz(cm2_noise **out, const double *h_bands, int64_t la
                               const int64_t *h_sizes, int64_t nblocks, int method,
                               void *stream);
 int cm2_noise_destroy(cm2_noise *n);
-/* y = N^-1 v over all blocks (blk_matvec, blkop.py:195-206).  d_out != d_v. */
+/* y = N^-1 v over all blocks (blk_matvec, blkop.py:195-206).  d_out != d_v.  Nothing is built on the
+ * first application: the create call leaves the state of every method complete. */
 int cm2_noise_apply(cm2_noise *n, const double *d_v, double *d_out, void *stream);
 /* y = N^-1 v with v and y both in the tile-bucketed order of `tiles` (CM2_TOEPLITZ_FUSED
  * operators, and CM2_TOEPLITZ_AUTO ones with lambda <= 2049): the permutation to and from time order

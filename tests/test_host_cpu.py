@@ -434,3 +434,64 @@ def test_restartable_entry_points_exist_and_exclude_the_in_place_updates():
     for name in ("cm2_axpy", "cm2_scal", "cm2_Z_axpy", "cm2_panel_gemm", "cm2_pcg_update_p", "cm2_pcg_update_xr",
                  "cm2_flag_samples", "cm2_pcg", "cm2_pcg_sharded", "cm2_arnoldi", "cm2_compact_f64"):
         assert name not in _hip.RESTARTABLE
+
+
+def _csrc_texts():
+    d = os.path.join(ROOT, "cosmomap2_amd", "csrc")
+    return {f: open(os.path.join(d, f)).read() for f in sorted(os.listdir(d)) if f.endswith((".h", ".hip"))}
+
+
+# `return <digit>;` as a status: in the body of a macro, or right after a set_error(...) / upload(...) call
+# (`set_error("..."); return 1;`, `if (upload(...)) return 1;`).  A count such as policy::parts_of's
+# `return 1` follows neither.
+_LITERAL_RETURN = re.compile(r"\breturn\s+[1-9]\s*;")
+_LITERAL_AFTER_CALL = re.compile(r"\b(?:set_error|upload)\s*\([^;]*?\)\s*[;)]\s*(?:\}\s*)?return\s+[1-9]\s*;")
+
+
+def _macro_bodies(text):
+    lines, out, k = text.split("\n"), [], 0
+    while k < len(lines):
+        if lines[k].lstrip().startswith("#define"):
+            body = [lines[k]]
+            while lines[k].rstrip().endswith("\\") and k + 1 < len(lines):
+                k += 1
+                body.append(lines[k])
+            out.append("\n".join(body))
+        k += 1
+    return out
+
+
+def test_status_codes_are_named_and_rocfft_has_one_home():
+    """The status vocabulary of csrc/: only CM2_HIP (cm2_common.h) reports out of memory, no macro and no
+    failure path returns a literal number, and rocFFT's set-up and plans live in cm2_rocfft.h alone."""
+    texts = _csrc_texts()
+    assert len(texts) >= 20 and "cm2_rocfft.h" in texts
+    # the patterns see what they are meant to see
+    assert _LITERAL_AFTER_CALL.search('set_error("x %d", (int)s);\n        return 3;')
+    assert _LITERAL_AFTER_CALL.search('if (A(c, x)) { set_error("failed"); return 1; }')
+    assert _LITERAL_AFTER_CALL.search("if (upload(&f->d_len, h_len, (size_t)nseg, st)) return 1;")
+    assert not _LITERAL_AFTER_CALL.search("if (int rc = upload(&f->d_len, h_len, (size_t)nseg, st)) return rc;")
+    assert [m for m in _macro_bodies("#define F(c) \\\n  do { \\\n    return 3; \\\n  } while (0)\nint x;")
+            if _LITERAL_RETURN.search(m)]
+    oom = "return CM2_ERR_OUT_OF_MEMORY"
+    assert {f: t.count(oom) for f, t in texts.items() if oom in t} == {"cm2_common.h": 1}
+    for f, t in texts.items():
+        assert not [m for m in _macro_bodies(t) if _LITERAL_RETURN.search(m)], f
+        hit = _LITERAL_AFTER_CALL.search(t)
+        assert hit is None, (f, hit.group(0)[-60:])
+    assert "return 1;" in texts["cm2_plan_policy.h"]           # the count of policy::parts_of stays
+    for word in ("rocfft_setup", "rocfft_plan_create"):
+        assert [f for f, t in texts.items() if word in t] == ["cm2_rocfft.h"], word
+
+
+def test_library_does_not_export_the_tile_plan_accessors():
+    """The units that read a tile plan include cm2_tiles.h; the C accessors that stood in for the include are gone."""
+    import subprocess
+    from cosmomap2_amd import _hip
+    out = subprocess.run(["nm", "-D", "--defined-only", _hip.LIB_PATH], check=True, capture_output=True,
+                         text=True).stdout
+    names = {ln.split()[-1] for ln in out.splitlines() if ln.strip()}
+    assert "cm2_tiles_create" in names and "cm2_noise_apply_tiles" in names
+    for s in ("cm2_tiles_index", "cm2_tiles_nt", "cm2_tiles_plan_id", "cm2_tiles_ntiles", "cm2_tiles_nvalid",
+              "cm2_tiles_offsets"):
+        assert s not in names, s
