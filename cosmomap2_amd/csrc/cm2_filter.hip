@@ -142,8 +142,12 @@ __global__ __launch_bounds__(256) void k_filter_mean(int64_t nseg, const int64_t
 // Discrete orthogonal polynomials on the unflagged samples of a chunk (Stieltjes three-term
 // recurrence).  They span the same space as the Legendre columns restricted to those samples,
 // so sum_k q_k q_k^T is the projector Q Q^T the reference gets from qr(legendres[unflagged])
-// (:307-315), without forming a Gram matrix: the basis is orthonormal to rounding whatever the
-// conditioning of the restricted Legendre block.  Per chunk: xc, xs (sample index -> [-1,1] on
+// (:307-315), without forming a Gram matrix: the basis does not inherit the conditioning of the
+// restricted Legendre block (1e5 to 1e11 for a short run of unflagged samples).  It is not
+// orthonormal to rounding for every flag pattern: against an extended-precision projector the
+// float64 recurrence is off by up to ~500 x 2^-53 S on the chunks of tests/_filter_ref.py, the
+// worst being unflagged samples in two clusters at the chunk's ends and exactly K of them, some
+// close together (S = |d| + |Q| |Q|^T |d|).  Per chunk: xc, xs (sample index -> [-1,1] on
 // the support of the unflagged samples), alpha[K], beta[K], 1/||p_k||[K].
 template <int K>
 struct OrthoCoef {

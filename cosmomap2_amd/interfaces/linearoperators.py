@@ -1019,7 +1019,8 @@ class FilterLO(_DeviceOp):
         sizes = []
         for array in self.subscans:
             for i in np.asarray(array).reshape(-1):
-                if int(i) not in sizes:
+                # a zero-length sub-scan has no table (filter_plan skips it; nrm2 of nothing raises)
+                if int(i) > 0 and int(i) not in sizes:
                     sizes.append(int(i))
         self.legendres = {n: get_legendre_polynomials(self.poly_order, n) for n in sizes}
 
