@@ -31,7 +31,8 @@
 // (0.75-0.80 ms) and were removed in round 4.
 // The geometry and the host's decisions are in cm2_os_policy.h, the lists' structures and their plan-time
 // builders in cm2_os_lists.h / cm2_os_lists.hip.  This translation unit is compiled with FMA contraction
-// ON (results are compared with the direct sum at 1e-12, not bit for bit).
+// ON (results are not promised bit for bit: every element is held to c 2^-53 B_i, B_i = A1 ||window||_2 / sqrt(W)
+// against an extended-precision band sum, tests/_noise_ref.py and tests/test_gpu_noise_kernels.py).
 #include "cm2_os_lists.h"
 
 #include <cstring>
