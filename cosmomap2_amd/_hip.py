@@ -133,6 +133,17 @@ PROTOTYPES = {
     "cm2_gaps_tiles_to_time": [_vp, _vp, _vp, _vp, _vp, _vp],
     "cm2_gaps_time_to_tiles": [_vp, _vp, _vp, _vp, _vp, _vp],
     "cm2_PtNP_gaps_apply": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "cm2_offsets_create": [ctypes.POINTER(_vp), _vp, _i64, ctypes.POINTER(_i64), _i64, _i64, ctypes.POINTER(_dbl),
+                           _vp],
+    "cm2_offsets_destroy": [_vp],
+    "cm2_offsets_info": [_vp, ctypes.POINTER(_i64)],
+    "cm2_offsets_counts": [_vp, _vp, _vp, _vp],
+    "cm2_offsets_expand": [_vp, _vp, _int, _vp, _vp],
+    "cm2_offsets_residual": [_vp, _vp, _vp, _int, _vp, _vp],
+    "cm2_offsets_sum": [_vp, _vp, _int, _vp, _vp],
+    "cm2_offsets_prepare_tiles": [_vp, _vp, _vp],
+    "cm2_offsets_to_tiles": [_vp, _vp, _vp, _int, _vp, _vp],
+    "cm2_offsets_from_tiles": [_vp, _vp, _vp, _int, _vp, _vp],
 }
 _RESTYPE = {"cm2_last_error": ctypes.c_char_p, "cm2_reduce_work_doubles": _i64,
             "cm2_gemm_tn_work_doubles": _i64}
@@ -209,6 +220,8 @@ RESTARTABLE = frozenset([
     "cm2_gaps_create", "cm2_gaps_gather", "cm2_gaps_scatter", "cm2_gaps_normal_apply", "cm2_gaps_precond_apply",
     "cm2_gaps_masked_diff", "cm2_gaps_rhs", "cm2_gaps_finish", "cm2_gaps_fill_linear",
     "cm2_gaps_prepare_tiles", "cm2_gaps_tiles_to_time", "cm2_gaps_time_to_tiles", "cm2_PtNP_gaps_apply",
+    "cm2_offsets_create", "cm2_offsets_expand", "cm2_offsets_residual", "cm2_offsets_sum",
+    "cm2_offsets_prepare_tiles", "cm2_offsets_to_tiles", "cm2_offsets_from_tiles",
 ])
 
 

@@ -5,3 +5,4 @@ from .linearoperators import *                               # noqa: F401,F403
 from .blkop import BlockDiagonalLinearOperator               # noqa: F401
 from .deflationlib import *                                  # noqa: F401,F403
 from .gapaware import *                                      # noqa: F401,F403
+from .destriper import *                                     # noqa: F401,F403

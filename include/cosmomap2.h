@@ -670,6 +670,57 @@ int cm2_gaps_time_to_tiles(const cm2_gaps *g, const cm2_tiles *tiles, const doub
 int cm2_PtNP_gaps_apply(const cm2_tiles *tiles, cm2_noise *noise, const cm2_gaps *g, const double *d_z,
                         double *d_out, double *d_tb, double *d_time1, double *d_time2, void *stream);
 
+/* ---- n4: destriping -- the baseline-offset templates F and F^T ---------------------------
+ * The correlated noise is modelled as one constant ("offset") per baseline.  The stream has noise blocks of
+ * h_sizes[0..nblocks-1] samples (adding up to nt < 2^32 - 1); block b = [o_b, o_b + n_b) is cut into
+ * K_b = ceil(n_b / L) baselines, baseline (b, k) = [o_b + k L, min(o_b + (k + 1) L, o_b + n_b)) with the global index
+ * j = sum of K_b' over b' < b, plus k; na = sum of K_b < 2^31.  A sample is valid when d_pix[t] >= 0; w_b is the
+ * weight of block b (h_weights == NULL: 1), w_t = w_b on the valid samples and 0 on the flagged ones.
+ *     (F a)_t = a_j(t) on the valid samples, 0 on the flagged ones;   (F^T y)_j = sum of y_t over the valid t of j.
+ * `weighted` = 1 multiplies every output once by w_b (W F a, F^T W y: the weight is factored out of the sum), 0 does
+ * not.  The summation order of F^T is fixed by (nt, h_sizes, L) alone: windows of 8192 samples counted from t = 0,
+ * inside a window a fixed tree over chunks of 32 samples, a baseline's windows added in ascending order through a
+ * side buffer of two slots per window; no floating-point atomics.  The time-order and the tile-order forms give the
+ * same bits.
+ *
+ * cm2_offsets_create: the handle KEEPS d_pix (the caller keeps it alive and unchanged) and owns the block table,
+ * nvalid_j (counted on the device), wsum_j = w_b nvalid_j and the side buffer.  Refuses with CM2_ERR_ARGUMENT
+ * nt >= 2^32 - 1, na >= 2^31, L < 1, sizes that do not add up to nt, weights that are not positive and finite --
+ * before the device is touched.  Synchronises.
+ * cm2_offsets_info: h_info[8] = nt, nblocks, L, na, valid samples, windows, tile forms (0 not prepared, 1 on the
+ * plan's window lists, 2 per sample), LDS bytes of the window kernels.
+ * cm2_offsets_counts: h_nvalid[na], h_wsum[na] (either may be NULL).  Synchronises.
+ * cm2_offsets_expand:   d_out[t] = [w_b] d_a[j(t)] on the valid samples, 0 on the flagged ones (nt doubles).
+ * cm2_offsets_residual: d_out[t] = [w_b] (d_d[t] - d_a[j(t)]) on the valid samples (d_a == NULL: [w_b] d_d[t]), 0 on
+ * the flagged ones.  A select: what d_d holds at a flagged sample is loaded and dropped.  d_out may be d_d.
+ * cm2_offsets_sum:      d_out[j] = [w_b] (F^T d_y)_j (na doubles).  One handle must not run two sums at once (the
+ * side buffer).  None of the three allocates or synchronises.
+ *
+ * On a tile plan: cm2_offsets_prepare_tiles makes `tiles` the plan of the handle (keyed by the plan's id; a call for
+ * the plan already prepared returns at once).  Refuses with CM2_ERR_ARGUMENT a plan with another nt, one with another
+ * number of valid samples, and one whose flagged set differs from d_pix's (a device pass; the message names the
+ * first sample that differs).  Builds the plan's windowed permutation lists if they do not exist yet; a stream
+ * shorter than one window has none, and the handle then keeps nt doubles for the per-sample permutations.
+ * Allocates and synchronises.
+ * cm2_offsets_to_tiles:   d_tb = cm2_tod_time_to_tiles(cm2_offsets_expand(d_a)) in one kernel, bit for bit.
+ * cm2_offsets_from_tiles: d_out = cm2_offsets_sum(cm2_tod_tiles_to_time(d_tb)) in one kernel (and the combine),
+ * bit for bit.  After prepare: kernel launches only. */
+typedef struct cm2_offsets cm2_offsets;
+int cm2_offsets_create(cm2_offsets **out, const int32_t *d_pix, int64_t nt, const int64_t *h_sizes, int64_t nblocks,
+                       int64_t baseline_length, const double *h_weights, void *stream);
+int cm2_offsets_destroy(cm2_offsets *f);
+int cm2_offsets_info(const cm2_offsets *f, int64_t *h_info);
+int cm2_offsets_counts(const cm2_offsets *f, int64_t *h_nvalid, double *h_wsum, void *stream);
+int cm2_offsets_expand(const cm2_offsets *f, const double *d_a, int weighted, double *d_out, void *stream);
+int cm2_offsets_residual(const cm2_offsets *f, const double *d_d, const double *d_a, int weighted, double *d_out,
+                         void *stream);
+int cm2_offsets_sum(cm2_offsets *f, const double *d_y, int weighted, double *d_out, void *stream);
+int cm2_offsets_prepare_tiles(cm2_offsets *f, const cm2_tiles *tiles, void *stream);
+int cm2_offsets_to_tiles(const cm2_offsets *f, const cm2_tiles *tiles, const double *d_a, int weighted, double *d_tb,
+                         void *stream);
+int cm2_offsets_from_tiles(cm2_offsets *f, const cm2_tiles *tiles, const double *d_tb, int weighted, double *d_out,
+                           void *stream);
+
 #ifdef __cplusplus
 }
 #endif
