@@ -6,5 +6,6 @@ from .process_ces import *                                   # noqa: F401,F403
 from .healpy_functions import *                              # noqa: F401,F403
 from .IOfiles import *                                       # noqa: F401,F403
 from .noise_model import *                                   # noqa: F401,F403
+from .offset_prior import *                                  # noqa: F401,F403
 from .noise_sim import *                                     # noqa: F401,F403
 from .gap_fill import *                                      # noqa: F401,F403

@@ -720,6 +720,34 @@ int cm2_offsets_to_tiles(const cm2_offsets *f, const cm2_tiles *tiles, const dou
                          void *stream);
 int cm2_offsets_from_tiles(cm2_offsets *f, const cm2_tiles *tiles, const double *d_tb, int weighted, double *d_out,
                            void *stream);
+/* The destriper's noise model from a PSD: d_bands[b][0..lambda-1], the first row of the banded-Toeplitz prior
+ * C_a^-1 on the offsets of block b, and the white variance sigma_b^2 (the block's weight is w_b = 1 / sigma_b^2),
+ * from the row d_psd[b][0..n/2] of a one-sided PSD (cm2_psd_welch), n = nperseg a power of two in [256, 65536],
+ * baseline length L >= 1.  Per block:
+ *   1. S_k = P_k fs / m_k (m_k = 1 at k = 0 and n/2, else 2), S_0 := S_1, as cm2_noise_bands_from_psd.  A bin with
+ *      S <= 0 or not finite fails with CM2_ERR_ARGUMENT and a message naming the block and the bin (the first in
+ *      block-major order).
+ *   2. sigma^2 = h_sigma2_in[b], positive and finite, or (h_sigma2_in NULL)
+ *      sigma^2 = (4/n) sum_{k = n/4}^{n/2 - 1} S_k.
+ *   3. R_k = max(S_k - sigma^2, 0), the correlated part.
+ *   4. q_j = (1/n) sum_{k = 0}^{n/2} m_k R_k D_k cos(w_k L j), j = 0 .. K-1, K = floor((n/2 + 1) / L),
+ *      w_k = 2 pi k / n, D_k = sin^2(L w_k / 2) / (L^2 sin^2(w_k / 2)), D_0 = 1: the covariance of the means of two
+ *      baselines j apart, (1/L^2) sum_{|s| < L} (L - |s|) r_{|jL + s|} with r = irfft(R, n), in closed form; no lag
+ *      beyond n/2 is used.  K < 2 is refused (the message gives the smallest nperseg that would do).
+ *   5. Q_i = q~_0 + 2 sum_{j = 1}^{K-1} q~_j cos(2 pi i j / M), q~_j = (1 - j/K) q_j, i = 0 .. M/2, M the smallest
+ *      power of two >= 2K: the offsets' spectrum, >= 0 by the Bartlett taper (a Fejer-smoothed symbol).
+ *   6. H_i = 1 / max(Q_i, floor sigma^2 / L), floor in (0, 1]: sigma^2 / L is the white variance of a baseline
+ *      mean, so the prior is bounded by wsum / floor.
+ *   7. band_i = (1 - i/lambda) (1/M) sum_{k = 0}^{M/2} m'_k H_k cos(2 pi i k / M), i = 0 .. lambda-1,
+ *      1 <= lambda <= M/2, m' like m on M: the second Bartlett taper makes every block SPD.
+ *   8. Every sum runs in increasing index order in one accumulator; the angles are reduced in integers before
+ *      cospi / sinpi.  A block gives the same bits alone and inside a group.
+ * A short last baseline of a block, or one with flagged samples, is treated like a full one.
+ * Every bad argument is refused before the device is touched.  Overwrites d_bands[nb][lambda] and, when it is not
+ * NULL, h_sigma2_out[nb] (host); synchronises. */
+int cm2_offset_prior_from_psd(const double *d_psd, int64_t nb, int64_t nperseg, double fsample,
+                              int64_t baseline_length, int64_t lambda, const double *h_sigma2_in /* NULL: estimate */,
+                              double floor, double *d_bands, double *h_sigma2_out /* may be NULL */, void *stream);
 
 #ifdef __cplusplus
 }
