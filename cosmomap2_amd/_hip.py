@@ -104,6 +104,10 @@ PROTOTYPES = {
     "cm2_fullsky_to_cutsky": [_int, _i64, _vp, _vp, _i64, _vp, _vp],
     "cm2_ground_bin_sums": [_i64, _int, _vp, _vp, _vp, _vp],
     "cm2_ground_subtract": [_i64, _vp, _vp, _vp, _vp, _vp],
+    "cm2_ground_sums_create": [ctypes.POINTER(_vp), _int, _vp],
+    "cm2_ground_sums_destroy": [_vp],
+    "cm2_ground_sums_info": [_vp, ctypes.POINTER(_i64)],
+    "cm2_ground_sums_apply": [_vp, _i64, _vp, _vp, _int, _vp, _vp],
     "cm2_psd_create": [ctypes.POINTER(_vp), _i64, _int, _i64, _vp],
     "cm2_psd_destroy": [_vp],
     "cm2_psd_info": [_vp, ctypes.POINTER(_i64)],
@@ -217,6 +221,7 @@ RESTARTABLE = frozenset([
     "cm2_transpose", "cm2_cos_sin_2phi", "cm2_m2_finish",
     "cm2_filter_create", "cm2_filter_apply", "cm2_filter_apply_tiles",
     "cm2_cutsky_to_fullsky", "cm2_fullsky_to_cutsky", "cm2_ground_bin_sums", "cm2_ground_subtract",
+    "cm2_ground_sums_create", "cm2_ground_sums_apply",
     "cm2_psd_create", "cm2_psd_welch", "cm2_noise_bands_from_psd",
     "cm2_rng_fill", "cm2_noise_filter_from_psd", "cm2_noise_sim_create",
     "cm2_gaps_create", "cm2_gaps_gather", "cm2_gaps_scatter", "cm2_gaps_normal_apply", "cm2_gaps_precond_apply",

@@ -1093,12 +1093,47 @@ class FilterLO(_DeviceOp):
 
 
 # ============================================================== GroundFilterLO ===
+class _GroundSums(object):
+    """Owns a cm2_ground_sums handle: the order-independent bin sums of include/cosmomap2.h (f2b)."""
+
+    def __init__(self, nbins):
+        self.h = None
+        self.nbins = int(nbins)
+        h = ctypes.c_void_p()
+        _hip.call("cm2_ground_sums_create", ctypes.byref(h), self.nbins, D.stream())
+        self.h = h
+
+    def info(self):
+        info = (ctypes.c_int64 * 4)()
+        _hip.call("cm2_ground_sums_info", self.h, info)
+        return dict(zip(("nbins", "lds_bins", "lds_bytes", "route"), [int(v) for v in info]))
+
+    def apply(self, nt, d_bin, d_v, route=0):
+        sums = D.empty(self.nbins)
+        _hip.call("cm2_ground_sums_apply", self.h, int(nt), D.ptr(d_bin), D.ptr(d_v), int(route), D.ptr(sums),
+                  D.stream())
+        return sums
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            try:
+                _hip.load().cm2_ground_sums_destroy(self.h)
+            except Exception:
+                pass
+            self.h = None
+
+
 class GroundFilterLO(_DeviceOp):
     """
     Ground-template filter ``v - G (G^T G)^-1 G^T v`` (reference: linearoperators.py:24-61):
     ``ground[t]`` is the azimuth bin of sample t (-1 = none), ``G`` the pol=1 pointing
     onto ``max(ground)+1`` bins and ``(G^T G)^-1`` the inverse hit count per bin (empty
     bins give 0, :788-790).
+
+    ``reproducible=True``: ``G^T v`` is formed as exact integer sums (``cm2_ground_sums_apply``), so the
+    filter gives the same bits on every run, on the time order and on the tile order, for any number of
+    bins; a NaN or Inf in a binned sample then poisons every bin, not only its own.  The default
+    (``False``) adds fp64 terms in an order that changes from run to run.
     """
 
     def counts_in_groundbins(self, g):
@@ -1110,7 +1145,10 @@ class GroundFilterLO(_DeviceOp):
     LDS_BINS = 8192          # cm2_ground_bin_sums keeps one histogram per workgroup in LDS
 
     def _bin_sums(self, x):
-        """G^T x: LDS histogram when the bins fit, else the pixel-major P^T of SparseLO."""
+        """G^T x: LDS histogram when the bins fit, else the pixel-major P^T of SparseLO; the exact
+        integer sums in reproducible mode."""
+        if self._sums is not None:
+            return self._sums.apply(self.n, self._G._d_pix, x)
         if self.nbins > self.LDS_BINS:
             return self._G.rmult(x)
         sums = D.empty(self.nbins)
@@ -1139,7 +1177,7 @@ class GroundFilterLO(_DeviceOp):
         subtraction do not care about the order of the samples, only the bin labels have to
         be carried over once.  Flagged-pixel samples are absent there; they hold 0 in the
         chain P^T (.) P, so the bin sums are the same."""
-        if self.nbins > self.LDS_BINS or T.nt != self.n:
+        if (self.nbins > self.LDS_BINS and self._sums is None) or T.nt != self.n:
             return False
         cache = getattr(self, "_bin_tb", None)
         if cache is None or cache[0] is not T:
@@ -1148,20 +1186,29 @@ class GroundFilterLO(_DeviceOp):
             cache = self._bin_tb = (T, lab)
         lab = cache[1]
         st = D.stream()
-        sums = D.empty(self.nbins)
-        _hip.call("cm2_ground_bin_sums", T.nvalid, self.nbins, D.ptr(lab), D.ptr(d_in_tb),
-                  D.ptr(sums), st)
+        if self._sums is not None:
+            sums = self._sums.apply(T.nvalid, lab, d_in_tb)
+        else:
+            sums = D.empty(self.nbins)
+            _hip.call("cm2_ground_bin_sums", T.nvalid, self.nbins, D.ptr(lab), D.ptr(d_in_tb),
+                      D.ptr(sums), st)
         binned = self._invGtG.mult(sums)
         _hip.call("cm2_ground_subtract", T.nvalid, D.ptr(lab), D.ptr(binned), D.ptr(d_in_tb),
                   D.ptr(d_out_tb), st)
         return True
 
-    def __init__(self, ground):
+    def __init__(self, ground, reproducible=False):
+        if not isinstance(reproducible, bool):
+            raise ValueError("reproducible must be True or False, not %r" % (reproducible,))
+        self.reproducible = reproducible
+        self._sums = None                     # the cm2_ground_sums handle of the reproducible mode
         g = ground.detach().cpu().numpy() if D.is_tensor(ground) else np.asarray(ground)
         self.nbins = int(g.max()) + 1
         self.n = len(g)
         self._G = G = SparseLO(self.nbins, self.n, ground)
         G.counts = self.counts_in_groundbins(ground)
+        if reproducible:
+            self._sums = _GroundSums(self.nbins)
         self._invGtG = invGtG = BlockDiagonalPreconditionerLO(G, self.nbins)
         self.Pg = G * invGtG * G.T
         super(GroundFilterLO, self).__init__(nargin=self.n, nargout=self.n, matvec=self.mult,

@@ -505,6 +505,50 @@ int cm2_ground_bin_sums(int64_t nt, int nbins, const int32_t *d_bin, const doubl
 int cm2_ground_subtract(int64_t nt, const int32_t *d_bin, const double *d_binned,
                         const double *d_v, double *d_out, void *stream);
 
+/* ---- f2b: the same bin sums, bitwise reproducible  (GroundFilterLO(..., reproducible=True)) ----
+ * d_sums[b] = sum of d_v[t] over the samples with d_bin[t] == b, in place of the serial loop of the reference
+ * (linearoperators.py:394-400), as an ORDER-INDEPENDENT sum: the same bits run to run, for the time order and the
+ * tile order, for every permutation of the samples and every launch shape.  A sample counts when
+ * 0 <= d_bin[t] < nbins; every other label is skipped, as cm2_ground_bin_sums does.
+ *   1. Scale.  M = max over the counted samples of the bit pattern of |v_t| read as a uint64 (monotonic for
+ *      non-negative doubles; Inf and NaN sort above every finite value): one pass, one 64-bit atomic max on a
+ *      device word, exact and independent of the order.
+ *        M == 0, or no counted sample:        every sum is +0.0.
+ *        M >= 0x7FF0000000000000 (a counted sample is Inf or NaN): EVERY sum is NaN.  cm2_ground_bin_sums poisons
+ *                                             only the bins such a sample falls into; this route poisons them all.
+ *        otherwise e = (M >> 52) - 1023, so that every counted |v_t| < 2^(e+1).
+ *   2. Limbs.  Per counted sample, all in fp64 and all exact (scalings by powers of two with ldexp, subtractions
+ *      of a truncation):
+ *        y0 = ldexp(v, 31 - e), l0 = trunc(y0), r = y0 - l0;  y1 = ldexp(r, 32), l1 = trunc(y1), r = y1 - l1;
+ *        l2 = trunc(ldexp(r, 32)).
+ *      Each |l_k| < 2^32, all three carry the sign of v, and l0 2^64 + l1 2^32 + l2 = trunc(v 2^(95-e)).  Each
+ *      non-zero limb, converted to int64, is added to its bin's accumulator L_k with an unsigned 64-bit integer
+ *      atomic add (two's complement makes it signed).  Integer adds are exact: any order gives the same L_k.
+ *      nt < 2^31 keeps every |L_k| below 2^63.  The translation unit is compiled without FMA contraction.
+ *   3. Finish.  One thread per bin: S = L0 2^64 + L1 2^32 + L2 (|S| < 2^127) in 128-bit integers; of |S| the top
+ *      53 bits are kept, rounded to nearest, ties to even, on the rest; sum = +-ldexp(mant, shift + e - 95).
+ * So d_sums[b] is the correctly rounded sum of the truncated terms trunc(v_t 2^(95-e)) 2^(e-95).  Against the real
+ * sum it is off by at most half an ulp of the result plus hits_b 2^(e-95).  The bits are pinned for
+ * 2^-900 <= max |v_t| <= 2^900; outside, the recipe still defines the value, but the result may be subnormal or
+ * overflow and its last bit is not part of the contract.
+ *
+ * cm2_ground_sums_create: the handle owns 3 nbins int64 limbs and the scale word.  Allocates.
+ * cm2_ground_sums_info: h_info[4] = nbins, the bin limit of the LDS route (2048), the dynamic LDS bytes of the LDS
+ *   route at nbins (3 x 8 x nbins; 0 above the limit), the route that route = 0 takes (1 or 2).
+ * cm2_ground_sums_apply: overwrites d_sums[nbins].  route 1: three limb histograms per workgroup in LDS, then
+ *   integer atomics of the non-zero entries to the global limbs (nbins <= 2048); route 2: integer atomics straight to
+ *   the global limbs (any nbins); route 0: 1 where it fits, else 2.  Both routes give the same bits.  Clears its
+ *   state with a memset on the stream, then launches kernels only: it allocates nothing and does not synchronise.
+ *   One handle runs one apply at a time.
+ * Refused with CM2_ERR_ARGUMENT before any HIP call: NULL pointers (d_bin and d_v may be NULL when nt == 0),
+ * nbins < 1, nt < 0, nt >= 2^31, a route outside 0..2, route 1 with nbins > 2048. */
+typedef struct cm2_ground_sums cm2_ground_sums;
+int cm2_ground_sums_create(cm2_ground_sums **out, int nbins, void *stream);
+int cm2_ground_sums_destroy(cm2_ground_sums *h);
+int cm2_ground_sums_info(const cm2_ground_sums *h, int64_t *h_info);
+int cm2_ground_sums_apply(cm2_ground_sums *h, int64_t nt, const int32_t *d_bin, const double *d_v, int route,
+                          double *d_sums, void *stream);
+
 /* ---- f3: solution vector <-> full-sky HEALPix maps -------------------------------
  * cm2_cutsky_to_fullsky: d_full is pol arrays of nfull doubles one after the other
  * ([I | Q | U]); component k of observed pixel i, d_map[pol*i + k], goes to
