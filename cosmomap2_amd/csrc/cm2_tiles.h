@@ -121,7 +121,7 @@ struct cm2_tiles {
     double *d_cos = nullptr, *d_sin = nullptr;   // [nvalid]  (full-angle mode)
     // half-angle mode: ONE double per sample, h = sin / (1 + |cos|) (= tan of half the angle
     // folded into [-1, 1]) and the sign of cos in bit 15 of d_pl; cos = +-(1 - h^2)/(1 + h^2),
-    // sin = 2h/(1 + h^2) are rebuilt in the kernels (absolute error ~2e-16): 8 bytes less per
+    // sin = 2h/(1 + h^2) are rebuilt in the kernels (absolute error <= 3.4e-16): 8 bytes less per
     // sample in each of the two tile kernels
     bool half = false;
     double *d_half = nullptr;                    // [nvalid]

@@ -21,7 +21,7 @@
 //
 // P on TB order evaluates the reference's per-sample expression; with both angle arrays
 // (CM2_TILE_ANGLES=full) it is bit-identical to the reference loop, in the default half-angle
-// storage cos / sin are rebuilt to ~2e-16 absolute, so P agrees to rounding.
+// storage cos / sin are rebuilt to 3.4e-16 absolute, so P agrees to rounding.
 // P^T has two forms.  The default (k_Pt_tiles_fixed, CM2_PT_ORDER=fixed) adds the terms of every
 // pixel IN TIME ORDER starting from 0, exactly like the reference's serial loop, with no
 // atomics: bitwise reproducible from run to run and, with CM2_TILE_ANGLES=full, bit-identical to

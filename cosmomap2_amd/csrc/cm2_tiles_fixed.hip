@@ -2,7 +2,7 @@
 // ORDER starting from 0, exactly like the reference's serial scatter loop
 // (interfaces/linearoperators.py:394-400, :452-458, :509-516): no atomics, bitwise reproducible
 // from run to run, and bit-identical to the serial loop when the plan keeps cos and sin
-// (CM2_TILE_ANGLES=full; the default half-angle storage rebuilds them to ~2e-16).
+// (CM2_TILE_ANGLES=full; the default half-angle storage rebuilds them to 3.4e-16).
 //
 // ONE workgroup owns a tile from its first sample to its last: the tile's accumulators stay in
 // LDS for the whole bucket and are written out once with plain stores.  The bucket is walked

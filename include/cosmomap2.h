@@ -148,7 +148,7 @@ int cm2_tiles_destroy(cm2_tiles *t);
 /* h_info[0..11] = nt, valid samples (= length of a TB-ordered TOD), tile pixels, tiles, items,
  * 1 if the plan stores one half-angle value per sample instead of cos and sin (done when every
  * (cos, sin) pair is on the unit circle to 1e-14; the kernels rebuild cos = +-(1-h^2)/(1+h^2),
- * sin = 2h/(1+h^2), absolute error ~2e-16, and read 8 bytes less per sample), 1 if P^T sums in
+ * sin = 2h/(1+h^2), absolute error <= 3.4e-16, and read 8 bytes less per sample), 1 if P^T sums in
  * fixed (time) order, the plan's id (unique per plan in this process), slice length of the
  * fixed-order lists (0 until the first P^T builds them), the bytes one fixed-order P^T is
  * designed to read (TOD + padded lists), then 1 and the padded sample count (the two fields of the

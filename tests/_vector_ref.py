@@ -65,8 +65,9 @@ def assert_bit_equal(got, want, what=""):
     got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
     assert got.shape == want.shape, "%s: shape %r != %r" % (what, got.shape, want.shape)
     bad = np.flatnonzero(bits(got).reshape(-1) != bits(want).reshape(-1))
-    assert bad.size == 0, "%s: %d of %d elements differ, first at %d: %r != %r" % (
-        what, bad.size, got.size, bad[0], got.reshape(-1)[bad[0]], want.reshape(-1)[bad[0]])
+    assert bad.size == 0, "%s: %d of %d elements differ, first at %d: %r (%s) != %r (%s)" % (
+        what, bad.size, got.size, bad[0], got.reshape(-1)[bad[0]], float(got.reshape(-1)[bad[0]]).hex(),
+        want.reshape(-1)[bad[0]], float(want.reshape(-1)[bad[0]]).hex())
 
 
 # --------------------------------------------------------------------- inputs ----

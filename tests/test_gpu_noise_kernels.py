@@ -46,11 +46,9 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _noise_ref as R  # noqa: E402
+from _guarded import Guarded  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-
-SENTINEL = 0x7FF8DEAD0000BEEF        # a NaN with a payload: no kernel produces these bits
-GUARD = 8                            # sentinels in front of and behind the data
 
 
 @pytest.fixture(scope="module")
@@ -61,35 +59,6 @@ def cm():
     from cosmomap2_amd import _hip, device
     from cosmomap2_amd.interfaces import linearoperators as L
     return SimpleNamespace(I=I, L=L, D=device, hip=_hip, torch=torch)
-
-
-class Guarded(object):
-    """n doubles in the middle of a sentinel-filled buffer; data=None: NaN (an output)"""
-
-    def __init__(self, cm, n, data=None):
-        torch = cm.torch
-        self.cm, self.n = cm, int(n)
-        self.buf = torch.full((GUARD + self.n + GUARD,), SENTINEL, dtype=torch.int64,
-                              device=cm.D.dev()).view(torch.float64)
-        self.v = self.buf[GUARD:GUARD + self.n]
-        if data is None:
-            self.v.fill_(float("nan"))
-        else:
-            self.v.copy_(cm.D.to_dev(np.ascontiguousarray(data, dtype=np.float64).reshape(-1)))
-
-    @property
-    def ptr(self):
-        return self.v.data_ptr()
-
-    def get(self):
-        self.cm.torch.cuda.synchronize()
-        return self.v.cpu().numpy().copy()
-
-    def intact(self, what):
-        raw = self.buf.view(self.cm.torch.int64)
-        assert bool((raw[:GUARD] == SENTINEL).all().item()) and \
-            bool((raw[GUARD + self.n:] == SENTINEL).all().item()), \
-            "%s: wrote outside its %d elements" % (what, self.n)
 
 
 def call(cm, name, *args):

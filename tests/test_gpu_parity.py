@@ -153,7 +153,7 @@ def test_tiled_pointing(cm, oracle, monkeypatch, pol, nt, npix, tp, angles):
     np.testing.assert_array_equal(back.cpu().numpy(), np.where(pairs >= 0, v, 0.0))
     # P^T, default = fixed order: every pixel's terms are added in time order starting from 0,
     # as in the reference's serial loop.  With both angle arrays that is the oracle's result bit
-    # for bit; with half angles it differs by the rebuilt cos / sin (~2e-16) but is still
+    # for bit; with half angles it differs by the rebuilt cos / sin (3.4e-16) but is still
     # bitwise reproducible from run to run.
     assert T.pt_fixed
     _hip.call("cm2_Pt_tiles_apply", T.h, D.ptr(v_tb), D.ptr(out), st)
