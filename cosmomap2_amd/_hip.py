@@ -150,6 +150,7 @@ PROTOTYPES = {
     "cm2_offsets_from_tiles": [_vp, _vp, _vp, _int, _vp, _vp],
     "cm2_offset_prior_from_psd": [_vp, _i64, _i64, _dbl, _i64, _i64, ctypes.POINTER(_dbl), _dbl, _vp,
                                   ctypes.POINTER(_dbl), _vp],
+    "cm2_pointing_expand": [_i64, _int, _vp, _vp, ctypes.POINTER(_dbl), _vp, _vp, _i64, _int, _vp, _vp, _vp, _vp],
 }
 _RESTYPE = {"cm2_last_error": ctypes.c_char_p, "cm2_reduce_work_doubles": _i64,
             "cm2_gemm_tn_work_doubles": _i64}
@@ -229,7 +230,7 @@ RESTARTABLE = frozenset([
     "cm2_gaps_prepare_tiles", "cm2_gaps_tiles_to_time", "cm2_gaps_time_to_tiles", "cm2_PtNP_gaps_apply",
     "cm2_offsets_create", "cm2_offsets_expand", "cm2_offsets_residual", "cm2_offsets_sum",
     "cm2_offsets_prepare_tiles", "cm2_offsets_to_tiles", "cm2_offsets_from_tiles",
-    "cm2_offset_prior_from_psd",
+    "cm2_offset_prior_from_psd", "cm2_pointing_expand",
 ])
 
 

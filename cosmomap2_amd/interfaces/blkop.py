@@ -43,11 +43,17 @@ class BlockDiagonalLinearOperator(LinearOperator):
         self._nargins, self._nargouts = nargins, nargouts
         log = kwargs.get("logger", null_log)
         log.debug("Building new BlockDiagonalLinearOperator")
-        mv = fused if fused is not None else (lambda x: self._blk_matvec(x, False))
-        rmv = None if symmetric else (lambda x: self._blk_matvec(x, True))
+        mv = fused if fused is not None else self._blk_forward          # (bound methods, not closures over self:
+        rmv = None if symmetric else self._blk_transposed               #  linop.LinearOperator keeps them unbound)
         super(BlockDiagonalLinearOperator, self).__init__(
             sum(nargins), sum(nargouts), mv, rmatvec=rmv, symmetric=symmetric, dtype=op_dtype,
             **kwargs)
+
+    def _blk_forward(self, x):
+        return self._blk_matvec(x, False)
+
+    def _blk_transposed(self, x):
+        return self._blk_matvec(x, True)
 
     def _blk_matvec(self, x, transposed):
         nin = self._nargouts if transposed else self._nargins

@@ -22,6 +22,8 @@ applied (see interfaces/linearoperators.py: ``_fuse_chain``).
 """
 import logging
 import numbers
+import types
+import weakref
 
 import numpy as np
 
@@ -98,30 +100,45 @@ class LinearOperator(BaseLinearOperator):
     def __init__(self, nargin, nargout, matvec, rmatvec=None, matvec_transp=None,
                  matvec_adj=None, symmetric=False, **kwargs):
         super(LinearOperator, self).__init__(nargin, nargout, symmetric=symmetric, **kwargs)
-        self.__matvec = matvec
-        transp = rmatvec or matvec_transp or matvec_adj
+        # An operator must not refer to itself: it would be cyclic garbage when it is dropped, and the device
+        # buffers it owns would stay allocated until the cycle collector happens to run.  So a bound method of
+        # this object is kept as its function, a symmetric operator does not store itself as its transpose, the
+        # transpose (which refers to this operator) is held weakly and made again when it is gone, and _chain is
+        # a property.
+        self.__matvec, self.__own = self.__unbound(matvec)
         if "device_ok" in kwargs:
             self._device_ok = bool(kwargs["device_ok"])
         self._is_transpose = "_transpose_of" in kwargs
-        if self._is_transpose:
-            self.__T = kwargs["_transpose_of"]
-        elif self.symmetric:
-            self.__T = self
-        elif transp is not None:
-            self.__T = LinearOperator(nargout, nargin, transp, symmetric=False,
-                                      dtype=kwargs.get("dtype", np.float64),
-                                      logger=self.logger, _transpose_of=self,
-                                      device_ok=supports_device(self))
-        else:
-            self.__T = None
-        self._chain = [self]
+        self.__parent = kwargs.get("_transpose_of")
+        self.__transp, self.__own_transp = self.__unbound(
+            None if self._is_transpose else (rmatvec or matvec_transp or matvec_adj))
+        self.__Tref = None
+        self.__tkw = dict(dtype=kwargs.get("dtype", np.float64))
+
+    _chain = property(lambda self: [self])
+
+    def __unbound(self, fn):
+        """(fn, False), or (the function of fn, True) when fn is a bound method of this operator."""
+        if fn is not None and getattr(fn, "__self__", None) is self and hasattr(fn, "__func__"):
+            return fn.__func__, True
+        return fn, False
 
     # -- transposes ---------------------------------------------------------------
     @property
     def T(self):
-        if self.__T is None:
+        if self._is_transpose:
+            return self.__parent
+        if self.symmetric:
+            return self
+        if self.__transp is None:
             raise NotImplementedError("transpose of this operator is not defined")
-        return self.__T
+        t = self.__Tref() if self.__Tref is not None else None
+        if t is None:
+            transp = types.MethodType(self.__transp, self) if self.__own_transp else self.__transp
+            t = LinearOperator(self.nargout, self.nargin, transp, symmetric=False, logger=self.logger,
+                               _transpose_of=self, device_ok=supports_device(self), **self.__tkw)
+            self.__Tref = weakref.ref(t)
+        return t
 
     H = T           # real operators only on this path
 
@@ -139,7 +156,7 @@ class LinearOperator(BaseLinearOperator):
             return self.matvec(x[:, 0]).reshape(-1, 1)
         self._check(x)
         self._nMatvec += 1
-        return self.__matvec(x)
+        return self.__matvec(self, x) if self.__own else self.__matvec(x)
 
     def rmatvec(self, x):
         return self.T.matvec(x)
@@ -242,7 +259,8 @@ class _Product(LinearOperator):
             rmatvec=(self._apply_T if transposable else None), symmetric=False,
             dtype=np.result_type(*[f.dtype for f in self._factors]),
             device_ok=all(supports_device(f) for f in self._factors))
-        self._chain = self._factors
+
+    _chain = property(lambda self: self._factors)
 
     def _compiled(self):
         if self._plan is None:

@@ -9,3 +9,4 @@ from .noise_model import *                                   # noqa: F401,F403
 from .offset_prior import *                                  # noqa: F401,F403
 from .noise_sim import *                                     # noqa: F401,F403
 from .gap_fill import *                                      # noqa: F401,F403
+from .pointing_expand import *                               # noqa: F401,F403

@@ -14,7 +14,7 @@ float32 columns of 1024 pixels per row named TEMPERATURE, Q_POLARISATION, U_POLA
 """
 import numpy as np
 
-__all__ = ["read_map", "write_map", "FitsFormatError", "nest2ring", "ring2nest", "reorder"]
+__all__ = ["read_map", "write_map", "FitsFormatError", "nest2ring", "ring2nest", "reorder", "vec2pix", "pix2vec"]
 
 _BLOCK = 2880
 _TYPES = {"E": ">f4", "D": ">f8", "J": ">i4", "K": ">i8", "I": ">i2", "B": "u1", "L": "u1"}
@@ -102,6 +102,113 @@ def reorder(m, n2r=False, r2n=False):
     else:
         out[...] = m[..., perm]
     return out
+
+
+# ------------------------------------------------------------ direction <-> pixel ------
+def _spread_bits(v):
+    """Bits of v (< 2^32) moved to the even positions (the inverse of _compact_bits)."""
+    v = v & 0x00000000FFFFFFFF
+    v = (v | (v << 16)) & 0x0000FFFF0000FFFF
+    v = (v | (v << 8)) & 0x00FF00FF00FF00FF
+    v = (v | (v << 4)) & 0x0F0F0F0F0F0F0F0F
+    v = (v | (v << 2)) & 0x3333333333333333
+    v = (v | (v << 1)) & 0x5555555555555555
+    return v
+
+
+def vec2pix(nside, x, y, z, nest=False):
+    """``hp.vec2pix``: the pixel that contains the direction ``(x, y, z)`` (any positive length; arrays broadcast).
+    The same branches as the device kernel of ``expand_pointing`` (``cm2_pointing_expand`` in
+    ``include/cosmomap2.h``): the equatorial belt for ``|z| <= 2/3``, the caps with ``sqrt(3 (1 - |z|))`` up to
+    ``|z| = 0.99`` and with ``sin(theta) sqrt(3 / (1 + |z|))`` beyond."""
+    nside = _check_nside(nside)
+    x, y, z = np.broadcast_arrays(np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64),
+                                  np.asarray(z, dtype=np.float64))
+    shape = x.shape
+    x, y, z = x.reshape(-1), y.reshape(-1), z.reshape(-1)
+    norm = np.sqrt(x * x + y * y + z * z)
+    if not np.all(np.isfinite(norm) & (norm > 0)):
+        raise ValueError("directions must be finite and not zero")
+    x, y, z = x / norm, y / norm, z / norm
+    za = np.abs(z)
+    tt = np.arctan2(y, x) * (2.0 / np.pi)
+    tt = np.where(tt < 0, tt + 4.0, tt)
+    tt = np.where(tt >= 4.0, tt - 4.0, tt)
+    sth = np.sqrt(x * x + y * y)
+    belt = za <= 2.0 / 3.0
+    # equatorial belt
+    t1, t2 = nside * (0.5 + tt), nside * z * 0.75
+    jp_e, jm_e = np.floor(t1 - t2).astype(np.int64), np.floor(t1 + t2).astype(np.int64)
+    # caps
+    with np.errstate(invalid="ignore"):
+        tmp = np.where(za <= 0.99, nside * np.sqrt(3.0 * (1.0 - np.minimum(za, 1.0))),
+                       nside * sth * np.sqrt(3.0 / (1.0 + za)))
+    ntt = np.minimum(3, np.floor(tt).astype(np.int64))
+    tp = tt - ntt
+    jp_c, jm_c = np.floor(tp * tmp).astype(np.int64), np.floor((1.0 - tp) * tmp).astype(np.int64)
+    if nest:
+        ifp, ifm = jp_e // nside, jm_e // nside
+        face_e = np.where(ifp == ifm, ifp | 4, np.where(ifp < ifm, ifp, ifm + 8))
+        ix_e, iy_e = jm_e % nside, nside - (jp_e % nside) - 1
+        jp_c, jm_c = np.minimum(jp_c, nside - 1), np.minimum(jm_c, nside - 1)
+        north = z >= 0
+        face_c = np.where(north, ntt, ntt + 8)
+        ix_c, iy_c = np.where(north, nside - jm_c - 1, jp_c), np.where(north, nside - jp_c - 1, jm_c)
+        face, ix, iy = np.where(belt, face_e, face_c), np.where(belt, ix_e, ix_c), np.where(belt, iy_e, iy_c)
+        out = face * nside * nside + (_spread_bits(ix) | (_spread_bits(iy) << 1))
+    else:
+        nl4, ncap, npix = 4 * nside, 2 * nside * (nside - 1), 12 * nside * nside
+        ir_e = nside + 1 + jp_e - jm_e
+        ip_e = ((jp_e + jm_e - nside + (1 - (ir_e & 1)) + 1) // 2) % nl4
+        pix_e = ncap + (ir_e - 1) * nl4 + ip_e
+        ir_c = jp_c + jm_c + 1
+        ip_c = np.floor(tt * ir_c).astype(np.int64) % (4 * ir_c)
+        pix_c = np.where(z > 0, 2 * ir_c * (ir_c - 1) + ip_c, npix - 2 * ir_c * (ir_c + 1) + ip_c)
+        out = np.where(belt, pix_e, pix_c)
+    return out.reshape(shape) if shape else int(out[0])
+
+
+def pix2vec(nside, ipix, nest=False):
+    """``hp.pix2vec``: the unit vectors ``(x, y, z)`` of the centres of pixel(s) ``ipix``."""
+    nside = _check_nside(nside)
+    ip = np.asarray(ipix, dtype=np.int64)
+    scalar = ip.ndim == 0
+    ip = ip.reshape(-1)
+    npix, ncap, nl4 = 12 * nside * nside, 2 * nside * (nside - 1), 4 * nside
+    if ip.size and (ip.min() < 0 or ip.max() >= npix):
+        raise ValueError("pixel index outside [0, %d)" % npix)
+    if nest:
+        ip = np.asarray(nest2ring(nside, ip), dtype=np.int64).reshape(-1)
+    fact2 = 4.0 / npix
+    north, south = ip < ncap, ip >= npix - ncap
+    # caps: ring iring (1 .. nside - 1) counted from the nearer pole, iphi 1 .. 4 iring
+    q = np.where(north, ip, npix - 1 - ip)                   # index counted from the nearer pole
+    iring = (1 + np.floor(np.sqrt(1.0 + 2.0 * q)).astype(np.int64)) >> 1
+    iring = np.where(2 * iring * (iring - 1) > q, iring - 1, iring)        # (the float sqrt may be one off)
+    iring = np.where(2 * iring * (iring + 1) <= q, iring + 1, iring)
+    iring = np.maximum(iring, 1)
+    within = q - 2 * iring * (iring - 1)                     # 0 .. 4 iring - 1, from the pole's side
+    iphi_cap = np.where(north, within + 1, 4 * iring - within)
+    tmp = np.where(north | south, iring * iring * fact2, 1.0)
+    z_cap = np.where(north, 1.0 - tmp, tmp - 1.0)
+    sth_cap = np.sqrt(tmp * (2.0 - tmp))
+    phi_cap = (iphi_cap - 0.5) * (np.pi / 2) / iring
+    # belt
+    e = ip - ncap
+    ir_b = e // nl4 + nside
+    iphi_b = e % nl4 + 1
+    fodd = np.where((ir_b + nside) & 1, 1.0, 0.5)
+    z_b = (2 * nside - ir_b) * (2.0 / (3.0 * nside))
+    phi_b = (iphi_b - fodd) * (np.pi / 2) / nside
+    cap = north | south
+    z = np.where(cap, z_cap, z_b)
+    sth = np.where(cap, sth_cap, np.sqrt((1.0 - z_b) * (1.0 + z_b)))
+    phi = np.where(cap, phi_cap, phi_b)
+    x, y = sth * np.cos(phi), sth * np.sin(phi)
+    if scalar:
+        return float(x[0]), float(y[0]), float(z[0])
+    shape = np.shape(ipix)
+    return x.reshape(shape), y.reshape(shape), z.reshape(shape)
 
 
 def _parse_header(data, pos):

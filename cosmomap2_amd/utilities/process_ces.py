@@ -66,13 +66,24 @@ class ProcessTimeSamples(object):
 
     ``allreduce``: optional callable applied in place to each per-pixel sum before the
     mask is formed (sums over TOD shards on other GPUs, see sharding.py).
+
+    ``cos_sin``: a pair of float64 device tensors ``(cos 2 phi, sin 2 phi)``, one element per sample, in place of
+    ``phi`` (``expand_pointing`` produces them); they are adopted without a copy.  Giving both raises.
     """
 
     def __init__(self, pixs, npix, obspix=None, pol=1, phi=None, w=None, ground=None,
-                 threshold_cond=1.e3, obspix2=None, allreduce=None):
+                 threshold_cond=1.e3, obspix2=None, allreduce=None, cos_sin=None):
         D.require_gpu()
         if pol not in (1, 2, 3):
             raise RuntimeError("No valid polarization key set!\t=>\tpol=%r" % (pol,))
+        if cos_sin is not None:
+            if phi is not None:
+                raise ValueError("give the angles as phi or as cos_sin, not both")
+            if len(cos_sin) != 2 or not all(
+                    D.is_dev(t) and t.dtype == torch.float64 and t.is_contiguous() and t.numel() == len(pixs)
+                    for t in cos_sin):
+                raise ValueError("cos_sin must be a pair of contiguous float64 device tensors (cos 2 phi, sin 2 phi) "
+                                 "with one element per sample (%d)" % len(pixs))
         self.pixs = pixs
         self.oldnpix = int(npix)
         self.nsamples = len(pixs)
@@ -95,7 +106,9 @@ class ProcessTimeSamples(object):
             self._d_pix = D.i32(pixs)                      # device copy (int32)
         self._d_w = None if w is None else D.f64(w)
         self._d_cos = self._d_sin = None
-        if pol > 1:
+        if pol > 1 and cos_sin is not None:
+            self._d_cos, self._d_sin = cos_sin             # adopted as they are (utilities/pointing_expand.py)
+        elif pol > 1:
             if phi is None:
                 raise RuntimeError("pol=%d needs the polarisation angles phi" % pol)
             if D.is_tensor(phi):

@@ -793,6 +793,43 @@ int cm2_offset_prior_from_psd(const double *d_psd, int64_t nb, int64_t nperseg, 
                               int64_t baseline_length, int64_t lambda, const double *h_sigma2_in /* NULL: estimate */,
                               double floor, double *d_bands, double *h_sigma2_out /* may be NULL */, void *stream);
 
+/* Pointing expansion: one boresight quaternion per time sample and one offset quaternion per detector ->
+ * d_pix[k ns + i], d_cos[k ns + i], d_sin[k ns + i] (detector-major), the arrays cm2_pointing_create,
+ * cm2_tiles_create and cm2_gaps_create read.  Quaternions are (x, y, z, w), scalar last, Hamilton product; every
+ * operation in IEEE double in the order written, nothing contracted:
+ *   1. q = (q_frame q_bore[i]) q_det[k] (without a frame: q_bore[i] q_det[k]), each component of a product p q
+ *      summed left to right:  x = pw qx + px qw + py qz - pz qy,  y = pw qy - px qz + py qw + pz qx,
+ *      z = pw qz + px qy - py qx + pz qw,  w = pw qw - px qx - py qy - pz qz.
+ *   2. n2 = ((xx + yy) + zz) + ww, r = 1 / n2: the one normalisation.
+ *      d = R(q) z^ = ((2 (x z + w y)) r, (2 (y z - w x)) r, ((ww + zz) - (xx + yy)) r), the line of sight;
+ *      o = R(q) x^ = (((ww + xx) - (yy + zz)) r, (2 (x y + w z)) r, (2 (x z - w y)) r), the sensitive direction.
+ *   3. The pixel is the HEALPix pixel of d (Gorski et al. 2005, ApJ 622, 759), nside a power of two <= 8192
+ *      (12 nside^2 < 2^31), RING (nest = 0) or NESTED: z = dz, t = atan2(dy, dx) (2/pi) wrapped into [0, 4)
+ *      (t < 0: t += 4; t >= 4: t -= 4).  |z| <= 2/3: jp = floor(nside (0.5 + t) - (nside z) 0.75),
+ *      jm = floor(nside (0.5 + t) + (nside z) 0.75).  Else tmp = nside sqrt(3 (1 - |z|)) while |z| <= 0.99 and
+ *      (nside sqrt(dx dx + dy dy)) sqrt(3 / (1 + |z|)) beyond, tp = t - min(3, floor(t)), jp = floor(tp tmp),
+ *      jm = floor((1 - tp) tmp), and in RING ordering ip = floor(t (jp + jm + 1)).  The NESTED bit interleave is
+ *      shifts and masks.
+ *   4. The angle psi is in the COSMO convention, from the local meridian pointing south toward east:
+ *      s2 = dx dx + dy dy, a = (ox (z dx) + oy (z dy)) - oz s2, b = oy dx - ox dy (s2 == 0: a = ox z, b = oy, the
+ *      meridian of longitude 0), den = a a + b b, cos 2 psi = (a a - b b) / den, sin 2 psi = (2 (a b)) / den
+ *      (den == 0: 1, 0).  No transcendental function on this path.
+ *   5. d_hwp (plate angle chi[i], rad): phi = psi + 2 chi; (c4, s4) = sincos(4 chi[i]) once per time sample,
+ *      cos 2 phi = c c4 - s s4, sin 2 phi = s c4 + c s4.  NULL: phi = psi.
+ *   6. Flagged: d_flags[i] != 0, or n2 is not a normal positive finite double (a boresight component that is not
+ *      finite, a zero boresight quaternion): pix = -1, cos = 1, sin = 0, the flag convention of every operator here.
+ * d_cos and d_sin both NULL: pixels only (pol = 1).  h_frame: 4 doubles on the host, NULL for none.  d_bore must be
+ * 16-byte aligned.  CM2_ERR_ARGUMENT, with every output untouched: nside not a power of two in [1, 8192], ndet < 1,
+ * ns < 0, exactly one of d_cos / d_sin, a frame quaternion (checked on the host) or a detector quaternion (checked
+ * by a kernel before the expansion is launched; the message names the first) whose n2 is not a normal positive
+ * finite double.  ns == 0 succeeds and writes nothing.  Synchronises once, on the detector check. */
+int cm2_pointing_expand(int64_t ns, int ndet, const double *d_bore /* [ns][4] */,
+                        const double *d_detquat /* [ndet][4], detector frame -> boresight frame */,
+                        const double *h_frame /* NULL: identity */, const double *d_hwp /* [ns] or NULL */,
+                        const uint8_t *d_flags /* [ns] or NULL */, int64_t nside, int nest,
+                        int32_t *d_pix /* [ndet ns] */, double *d_cos, double *d_sin /* [ndet ns] or both NULL */,
+                        void *stream);
+
 #ifdef __cplusplus
 }
 #endif
