@@ -151,6 +151,12 @@ PROTOTYPES = {
     "cm2_offset_prior_from_psd": [_vp, _i64, _i64, _dbl, _i64, _i64, ctypes.POINTER(_dbl), _dbl, _vp,
                                   ctypes.POINTER(_dbl), _vp],
     "cm2_pointing_expand": [_i64, _int, _vp, _vp, ctypes.POINTER(_dbl), _vp, _vp, _i64, _int, _vp, _vp, _vp, _vp],
+    "cm2_hwpss_create": [ctypes.POINTER(_vp), _i64, _int, _i64, ctypes.POINTER(_i64), _vp, _vp, _int, _vp],
+    "cm2_hwpss_destroy": [_vp],
+    "cm2_hwpss_info": [_vp, ctypes.POINTER(_i64)],
+    "cm2_hwpss_apply": [_vp, _vp, _vp, _vp],
+    "cm2_hwpss_fit": [_vp, _vp, _vp, _vp],
+    "cm2_hwpss_tables": [_vp, _vp, _vp, _vp],
 }
 _RESTYPE = {"cm2_last_error": ctypes.c_char_p, "cm2_reduce_work_doubles": _i64,
             "cm2_gemm_tn_work_doubles": _i64}
@@ -231,6 +237,7 @@ RESTARTABLE = frozenset([
     "cm2_offsets_create", "cm2_offsets_expand", "cm2_offsets_residual", "cm2_offsets_sum",
     "cm2_offsets_prepare_tiles", "cm2_offsets_to_tiles", "cm2_offsets_from_tiles",
     "cm2_offset_prior_from_psd", "cm2_pointing_expand",
+    "cm2_hwpss_create", "cm2_hwpss_apply", "cm2_hwpss_fit", "cm2_hwpss_tables",
 ])
 
 

@@ -30,7 +30,8 @@ torch = D.torch
 
 __all__ = ["SparseLO", "ToeplitzLO", "BlockLO", "BlockDiagonalLO",
            "BlockDiagonalPreconditionerLO", "InverseLO", "CoarseLO", "DeflationLO",
-           "TwoLevelPreconditionerLO", "FilterLO", "GroundFilterLO", "set_pointing_mode", "lp"]
+           "TwoLevelPreconditionerLO", "FilterLO", "GroundFilterLO", "HWPSSFilterLO", "hwpss_plan",
+           "set_pointing_mode", "lp"]
 
 _I64P = ctypes.POINTER(ctypes.c_int64)
 _DBLP = ctypes.POINTER(ctypes.c_double)
@@ -435,7 +436,7 @@ def _fuse_chain(chain):
                 i += 3
                 changed = True
                 continue
-            if i + 2 < n and chain[i + 2] is P and isinstance(chain[i + 1], (FilterLO, GroundFilterLO)) \
+            if i + 2 < n and chain[i + 2] is P and isinstance(chain[i + 1], (FilterLO, GroundFilterLO, HWPSSFilterLO)) \
                     and _use_tiles(P) and chain[i + 1]._tile_compatible(P):
                 # A = P^T F P, the production operator: tile-order P / P^T around the
                 # time-order filter (two streaming permutations instead of the exact-order
@@ -1213,3 +1214,132 @@ class GroundFilterLO(_DeviceOp):
         self.Pg = G * invGtG * G.T
         super(GroundFilterLO, self).__init__(nargin=self.n, nargout=self.n, matvec=self.mult,
                                              symmetric=True)
+
+
+# =============================================================== HWPSSFilterLO ===
+HWPSS_MAX_HARM = 8           # CM2_HWPSS_MAX_HARM of include/cosmomap2.h
+
+
+def hwpss_plan(ns, chunks=None):
+    """Chunk edges ``0 = e_0 < ... < e_C = ns`` of :class:`HWPSSFilterLO` (host only, no GPU).
+
+    ``chunks=None``: one chunk, the whole detector stream.  An int: chunks of that many samples, the last one
+    shorter when it does not divide ``ns``.  A 1-D array: the edges themselves, checked."""
+    ns = int(ns)
+    if ns < 1:
+        raise ValueError("ns must be >= 1, got %d" % ns)
+    if chunks is None:
+        return np.array([0, ns], dtype=np.int64)
+    if np.ndim(chunks) == 0:
+        n = int(chunks)
+        if n < 1 or n != chunks:
+            raise ValueError("the chunk length must be a positive integer, got %r" % (chunks,))
+        return np.append(np.arange(0, ns, n, dtype=np.int64), np.int64(ns))
+    e = np.asarray(chunks)
+    if e.ndim != 1 or e.size < 2 or not np.issubdtype(e.dtype, np.integer):
+        raise lp.ShapeError("chunk edges must be a 1-D integer array of at least two entries")
+    e = np.ascontiguousarray(e, dtype=np.int64)
+    if e[0] != 0 or e[-1] != ns or np.any(np.diff(e) <= 0):
+        raise ValueError("chunk edges must ascend strictly from 0 to ns=%d" % ns)
+    return e
+
+
+class _HWPSSHandle(object):
+    def __init__(self, handle, keep):
+        self.h = handle
+        self.keep = keep                   # the flag tensor the C side borrows
+
+    def __del__(self):
+        if self.h:
+            try:
+                _hip.load().cm2_hwpss_destroy(self.h)
+            except Exception:
+                pass
+            self.h = None
+
+
+class HWPSSFilterLO(_DeviceOp):
+    """
+    HWP-synchronous signal filter: per detector and chunk, fit the harmonics ``1, cos(n chi), sin(n chi)``,
+    ``n = 1..nharm``, of the half-wave plate angle to the unflagged samples and subtract them
+    (``M - M T G^-1 T^T M``, symmetric and idempotent; include/cosmomap2.h, f2c).  No counterpart in the reference.
+
+    ``HWPSSFilterLO(chi, pix_samples, ndet=1, nharm=4, chunks=None)``: ``chi[ns]`` the plate angle in radians, shared
+    by the detectors; ``pix_samples[ndet * ns]`` the pixel of every sample in the detector-major layout of
+    ``expand_pointing`` (< 0 = flagged; an HBM int32 tensor is adopted, not copied, and must not change afterwards);
+    ``chunks`` as :func:`hwpss_plan` takes them.  A unit (detector x chunk) with fewer than ``2 nharm + 1`` unflagged
+    samples, or whose harmonics are collinear on them (Cholesky pivot <= 2^-10 of its diagonal entry), is skipped:
+    its output and its coefficients are 0; ``filter_info()`` counts them.  Flagged samples are 0 in the output.
+    """
+
+    def __init__(self, chi, pix_samples, ndet=1, nharm=4, chunks=None):
+        if int(nharm) != nharm or not 1 <= int(nharm) <= HWPSS_MAX_HARM:
+            raise ValueError("nharm must be an integer in [1, %d], got %r" % (HWPSS_MAX_HARM, nharm))
+        if int(ndet) != ndet or int(ndet) < 1:
+            raise ValueError("ndet must be a positive integer, got %r" % (ndet,))
+        self.nharm, self.ndet = int(nharm), int(ndet)
+        self.K = 2 * self.nharm + 1
+        size = lambda a: int(a.numel()) if D.is_tensor(a) else int(np.size(a))
+        dims = lambda a: int(a.dim()) if D.is_tensor(a) else int(np.ndim(a))
+        if dims(chi) != 1 or size(chi) < 1:
+            raise lp.ShapeError("chi must be a 1-D array of at least one plate angle")
+        self.ns = size(chi)
+        self.n = self.ndet * self.ns
+        if size(pix_samples) != self.n:
+            raise lp.ShapeError("pix_samples has %d entries, expected ndet * len(chi) = %d"
+                                % (size(pix_samples), self.n))
+        self.edges = hwpss_plan(self.ns, chunks)
+        self.nchunks = int(self.edges.size) - 1
+        D.require_gpu()
+        self._d_pix = D.i32(pix_samples).reshape(-1)
+        d_chi = D.f64(chi)
+        handle = ctypes.c_void_p()
+        _hip.call("cm2_hwpss_create", ctypes.byref(handle), self.ns, self.ndet, self.nchunks,
+                  self.edges.ctypes.data_as(_I64P), D.ptr(d_chi), D.ptr(self._d_pix), self.nharm, D.stream())
+        self._handle = _HWPSSHandle(handle, self._d_pix)
+        super(HWPSSFilterLO, self).__init__(nargin=self.n, nargout=self.n, matvec=self.mult, symmetric=True)
+
+    def filter_info(self):
+        info = (ctypes.c_int64 * 9)()
+        _hip.call("cm2_hwpss_info", self._handle.h, info)
+        return dict(zip(("ns", "ndet", "nchunks", "nharm", "fitted", "skipped_few", "skipped_pivot",
+                         "segment", "segments"), [int(v) for v in info]))
+
+    def _input(self, d):
+        x = D.f64(d)
+        if x.numel() != self.n:
+            raise lp.ShapeError("time-domain vector has %d entries, expected %d" % (x.numel(), self.n))
+        return x
+
+    def mult(self, d):
+        x = self._input(d)
+        out = D.empty(self.n)
+        _hip.call("cm2_hwpss_apply", self._handle.h, D.ptr(x), D.ptr(out), D.stream())
+        return D.like_input(out, d)
+
+    _apply_all = mult
+
+    def coefficients(self, d):
+        """The fitted coefficients ``[ndet, nchunks, 2 nharm + 1]`` of ``d`` (zeros for a skipped unit), in the
+        order 1, cos chi, sin chi, cos 2 chi, ...; nothing is subtracted."""
+        x = self._input(d)
+        out = D.empty(self.ndet * self.nchunks * self.K)
+        _hip.call("cm2_hwpss_fit", self._handle.h, D.ptr(x), D.ptr(out), D.stream())
+        return D.like_input(out, d).reshape(self.ndet, self.nchunks, self.K)
+
+    def harmonic_tables(self):
+        """``(cos chi, sin chi)`` as the handle holds them (HBM tensors of ``ns`` doubles)."""
+        c, s = D.empty(self.ns), D.empty(self.ns)
+        _hip.call("cm2_hwpss_tables", self._handle.h, D.ptr(c), D.ptr(s), D.stream())
+        return c, s
+
+    def _tile_compatible(self, P):
+        """As for :class:`FilterLO`: the tile order has no slot for the samples ``P`` flags, so the filter may
+        stand between tile-order ``P`` and ``P^T`` only if it flags exactly the same samples."""
+        cache = self.__dict__.get("_flag_match")
+        if cache is None or cache[0]() is not P:
+            a, b = self._d_pix, P._d_pix
+            ok = a.numel() == b.numel() and (
+                a.data_ptr() == b.data_ptr() or bool(torch.equal(a < 0, b < 0)))
+            cache = self._flag_match = (weakref.ref(P), ok)
+        return cache[1]

@@ -549,6 +549,61 @@ int cm2_ground_sums_info(const cm2_ground_sums *h, int64_t *h_info);
 int cm2_ground_sums_apply(cm2_ground_sums *h, int64_t nt, const int32_t *d_bin, const double *d_v, int route,
                           double *d_sums, void *stream);
 
+/* ---- f2c: HWP-synchronous signal filter  (HWPSSFilterLO) ------------------------------------
+ * Fits and removes the harmonics of the half-wave plate angle, per detector and chunk.  No counterpart in the
+ * reference: the definition is the one below.
+ * Layout as cm2_pointing_expand writes it: nt = ndet ns, sample t of detector k at k ns + t.  d_chi[ns] is the plate
+ * angle in radians, shared by all detectors; a sample is flagged where d_pix[nt] < 0.  The chunk edges
+ * 0 = e_0 < e_1 < ... < e_C = ns cut the time axis, the same for every detector; a unit is one (detector, chunk) pair,
+ * unit k C + c.  Templates for H = nharm harmonics, 1 <= H <= CM2_HWPSS_MAX_HARM, K = 2 H + 1:
+ *     T_0 = 1,  T_{2n-1}(t) = cos(n chi_t),  T_{2n}(t) = sin(n chi_t)   (n = 1..H).
+ * Per unit, V its unflagged samples and m = |V|:
+ *     G = sum_{t in V} T(t) T(t)^T,   b = sum_{t in V} T(t) v_t,   c = G^-1 b,
+ *     out_t = v_t - T(t)^T c on V,  out_t = 0 on the flagged samples of the unit
+ * (M - M T G^-1 T^T M with M the mask: symmetric and idempotent).
+ * A unit is SKIPPED -- every sample of it 0 in the output, its K coefficients 0 -- when
+ *     m < K, or
+ *     the Cholesky factorisation G = L L^T meets a pivot p_j = G_jj - sum_{k<j} L_jk^2 <= CM2_HWPSS_TAU G_jj
+ *     (it stops at the first such pivot): the plate covered too little angle in the chunk, the harmonics are
+ *     collinear there and a fit would amplify rounding by 1 / pivot.
+ * A non-finite v_t on an unflagged sample makes its own unit's output non-finite and no other unit's.
+ *
+ * G depends on chi and the flags only: it is formed and factorised on the device by cm2_hwpss_create.  The handle
+ * holds the factors (K (K + 1) / 2 doubles per unit), the skip marks, the tables cos chi and sin chi (ns doubles
+ * each, device sincos, once) and the segment sums of one application (K doubles per segment).  The harmonics
+ * n >= 2 come from the two tables by c_n = c_{n-1} c_1 - s_{n-1} s_1, s_n = s_{n-1} c_1 + c_{n-1} s_1 in registers;
+ * nothing of size nt K is ever stored.
+ *
+ * Order of the sums (no floating-point atomics; the same bits every time): a unit is cut into segments of 4096
+ * samples (the last one shorter), one workgroup of 256 threads each.  Thread t adds T_j(q) v_q over its unflagged
+ * samples q = t, t + 256, ... of the segment in ascending order, starting from 0; the 64 lanes of a wave are added
+ * by x += x[lane + off], off = 32, 16, 8, 4, 2, 1; the four waves as ((w0 + w1) + w2) + w3; a unit's segments in
+ * ascending order, starting from 0.  The Gram sums are formed the same way.  Then the two triangular solves (row i:
+ * the known terms subtracted in ascending index order, then the division by L_ii), and
+ * out_t = v_t - (((c_0 + c_1 T_1) + c_2 T_2) + ... + c_{K-1} T_{K-1}).  Every product and sum is rounded on its own.
+ *
+ * cm2_hwpss_create keeps d_pix (it must not change or be freed while the handle lives) and copies what it needs of
+ *   d_chi.  h_edges[nchunks + 1].  Allocates and synchronises.
+ * cm2_hwpss_info: h_info[9] = ns, ndet, nchunks, nharm, units fitted, units skipped for m < K, units skipped for a
+ *   pivot, segment size, segments.
+ * cm2_hwpss_apply: d_out = F d_in (nt doubles each).  Three launches, no allocation, no synchronisation.  One handle
+ *   runs one apply or fit at a time.
+ * cm2_hwpss_fit: d_coeff[ndet nchunks K] = the coefficients c of every unit, without the subtract pass.
+ * cm2_hwpss_tables: copies the two tables to d_cos[ns], d_sin[ns].
+ * Refused with CM2_ERR_ARGUMENT, the outputs (and *out) untouched: nharm outside [1, 8]; ns, ndet or nchunks < 1;
+ * edges that do not ascend strictly from 0 to ns; NULL pointers; sizes that overflow the index types (ns >= 2^40,
+ * ndet ns > 2^46, 2^31 or more segments or units); d_out or d_coeff sharing memory with d_in. */
+#define CM2_HWPSS_TAU 0.0009765625          /* 2^-10 */
+#define CM2_HWPSS_MAX_HARM 8
+typedef struct cm2_hwpss cm2_hwpss;
+int cm2_hwpss_create(cm2_hwpss **out, int64_t ns, int ndet, int64_t nchunks, const int64_t *h_edges,
+                     const double *d_chi, const int32_t *d_pix, int nharm, void *stream);
+int cm2_hwpss_destroy(cm2_hwpss *h);
+int cm2_hwpss_info(const cm2_hwpss *h, int64_t *h_info);
+int cm2_hwpss_apply(cm2_hwpss *h, const double *d_in, double *d_out, void *stream);
+int cm2_hwpss_fit(cm2_hwpss *h, const double *d_in, double *d_coeff, void *stream);
+int cm2_hwpss_tables(const cm2_hwpss *h, double *d_cos, double *d_sin, void *stream);
+
 /* ---- f3: solution vector <-> full-sky HEALPix maps -------------------------------
  * cm2_cutsky_to_fullsky: d_full is pol arrays of nfull doubles one after the other
  * ([I | Q | U]); component k of observed pixel i, d_map[pol*i + k], goes to
