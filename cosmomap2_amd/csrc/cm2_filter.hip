@@ -6,9 +6,7 @@
 // second read of d comes from L2).  The wave also zero-fills the gap in front of its chunk, so
 // the output needs no separate memset: algorithmic traffic is 8 (d) + 4 (pix) + 8 (out) bytes
 // per sample.  The Legendre tables are shared by all chunks of one length and stay in L2.
-#include "cm2_tiles.h"
-
-#include <hipcub/hipcub.hpp>
+#include "cm2_perm_window.h"
 
 #include <vector>
 
@@ -341,7 +339,8 @@ __global__ __launch_bounds__(256) void k_filter_poly(int64_t nseg, const int64_t
 // run), filters the chunks in LDS -- one wavefront per chunk, same arithmetic as above -- and
 // scatters the window back through the list entries it kept in registers: 6 (list) + 8 + 8
 // bytes per sample.  Flagged samples have no slot in the tile order: they are simply absent.
-constexpr int kWinLen = 8192, kWinT = 256, kWinPer = kWinLen / kWinT;
+// The lists have the format of the plan's own (cm2_perm_window.h: kPermWin slots per window,
+// kPermT threads); only the windows differ, cut at chunk boundaries (FilterWin).
 
 struct FilterWin {
     int64_t t0;            // time of window offset 0
@@ -363,7 +362,7 @@ struct LdsChunk {
 };
 
 template <int K>          // K = 0: mean removal, K >= 2: Legendre order K - 1
-__global__ __launch_bounds__(kWinT, 2) void k_filter_windows(
+__global__ __launch_bounds__(kPermT, 2) void k_filter_windows(
     const FilterWin *__restrict__ wins, int nwin, const int64_t *__restrict__ start,
     const int64_t *__restrict__ len, const uint8_t *__restrict__ kind,
     const int64_t *__restrict__ toff, const double *__restrict__ table, const void *__restrict__ coef_,
@@ -372,33 +371,23 @@ __global__ __launch_bounds__(kWinT, 2) void k_filter_windows(
 {
     extern __shared__ double win_lds[];
     double *data = win_lds;
-    uint8_t *ok = reinterpret_cast<uint8_t *>(win_lds + kWinLen);
+    uint8_t *ok = reinterpret_cast<uint8_t *>(win_lds + kPermWin);
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int per_xcd = (nwin + 7) / 8;
-    const int wid = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
+    const int wid = window_of_workgroup(nwin);
     if (wid >= nwin) return;
     const FilterWin w = wins[wid];
-    for (int i = t; i < kWinLen / 8; i += kWinT) reinterpret_cast<uint64_t *>(ok)[i] = 0;
-    uint32_t kk[kWinPer];
-    uint16_t qq[kWinPer];
-    const int64_t base = (int64_t)wid * kWinLen;
-#pragma unroll
-    for (int u = 0; u < kWinPer; ++u) {
-        kk[u] = lst_k[base + t + u * kWinT];
-        qq[u] = lst_q[base + t + u * kWinT];
-    }
-    double vv[kWinPer];
-#pragma unroll
-    for (int u = 0; u < kWinPer; ++u) vv[u] = (kk[u] != kInvalidSample) ? in[kk[u]] : 0.0;
+    for (int i = t; i < kPermWin / 8; i += kPermT) reinterpret_cast<uint64_t *>(ok)[i] = 0;
+    WindowEntries e;
+    e.load(lst_k, lst_q, wid);
+    double vv[kPermPer];
+    e.gather(in, vv);
     __syncthreads();
-#pragma unroll
-    for (int u = 0; u < kWinPer; ++u)
-        if (kk[u] != kInvalidSample) {
-            data[qq[u]] = vv[u];
-            ok[qq[u]] = 1;
-        }
+    e.each_valid([data, ok, &vv](int u, uint32_t, uint16_t q) {     // (the pointers by value: see each_valid)
+        data[q] = vv[u];
+        ok[q] = 1;
+    });
     __syncthreads();
-    for (int s = w.s0 + wave; s < w.s1; s += kWinT / 64) {
+    for (int s = w.s0 + wave; s < w.s1; s += kPermT / 64) {
         const int64_t a = start[s] - w.t0, n = len[s];
         const int64_t prev = (s == w.s0) ? 0 : start[s - 1] + len[s - 1] - w.t0;
         zero_range(data, prev, a, lane);                       // gap in front of the chunk
@@ -420,9 +409,7 @@ __global__ __launch_bounds__(kWinT, 2) void k_filter_windows(
         }
     }
     __syncthreads();
-#pragma unroll
-    for (int u = 0; u < kWinPer; ++u)
-        if (kk[u] != kInvalidSample) out[kk[u]] = data[qq[u]];
+    e.each_valid([data, out](int, uint32_t k, uint16_t q) { out[k] = data[q]; });
 }
 
 // keys of the window lists: (window << 32) | position in the tile order, value = offset in the
@@ -432,24 +419,16 @@ __global__ __launch_bounds__(256) void k_win_keys(const FilterWin *__restrict__ 
                                                    uint64_t *__restrict__ keys,
                                                    uint16_t *__restrict__ vals)
 {
-    const int64_t total = nwin * kWinLen;
+    const int64_t total = nwin * kPermWin;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += stride) {
-        const int64_t wi = g / kWinLen;
-        const int q = (int)(g - wi * kWinLen);
+        const int64_t wi = g / kPermWin;
+        const int q = (int)(g - wi * kPermWin);
         const FilterWin w = wins[wi];
         const uint32_t k = q < w.span ? idx[w.t0 + q] : kInvalidSample;
         keys[g] = ((uint64_t)wi << 32) | (uint64_t)k;
         vals[g] = (uint16_t)q;
     }
-}
-
-__global__ __launch_bounds__(256) void k_win_unpack(int64_t total, const uint64_t *__restrict__ keys,
-                                                     uint32_t *__restrict__ lst_k)
-{
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += stride)
-        lst_k[g] = (uint32_t)(keys[g] & 0xFFFFFFFFull);
 }
 
 __global__ __launch_bounds__(256) void k_ground_subtract(int64_t nt, const int32_t *__restrict__ bin,
@@ -706,14 +685,14 @@ int filter_windows_build(cm2_filter *f, const uint32_t *d_idx, uint64_t plan_id,
     for (int64_t s0 = 0; s0 < nseg;) {
         const int64_t t0 = S[(size_t)s0];
         int64_t s1 = s0;
-        while (s1 < nseg && S[(size_t)s1] + L[(size_t)s1] - t0 <= kWinLen && s1 - s0 < (1 << 20)) ++s1;
+        while (s1 < nseg && S[(size_t)s1] + L[(size_t)s1] - t0 <= kPermWin && s1 - s0 < (1 << 20)) ++s1;
         if (s1 == s0) {                               // a chunk longer than a window: not tileable
             f->win_plan = plan_id;
             return 0;
         }
         int64_t t1 = S[(size_t)s1 - 1] + L[(size_t)s1 - 1];
         const int64_t next = s1 < nseg ? S[(size_t)s1] : f->nt;
-        if (next - t0 <= kWinLen) t1 = next;          // the trailing gap rides along (zeroed in LDS)
+        if (next - t0 <= kPermWin) t1 = next;          // the trailing gap rides along (zeroed in LDS)
         else f->win_memset = true;                    // samples between windows: zeroed by a memset
         FilterWin w;
         w.t0 = t0;
@@ -733,28 +712,10 @@ int filter_windows_build(cm2_filter *f, const uint32_t *d_idx, uint64_t plan_id,
     CM2_CHECK(f->nseg < ((int64_t)1 << 31) && f->nwin < ((int64_t)1 << 31), "too many chunks");
     CM2_HIP(cm2::dev_malloc(&f->d_wins, sizeof(FilterWin) * wins.size()));
     CM2_HIP(cm2::upload(f->d_wins, wins.data(), sizeof(FilterWin) * wins.size(), st));
-    const int64_t total = f->nwin * kWinLen;
-    DevTemp<uint64_t> keys_in, keys_out;
-    DevTemp<uint16_t> vals_in;
-    DevTemp<char> d_temp;
-    CM2_HIP(keys_in.alloc(total));
-    CM2_HIP(keys_out.alloc(total));
-    CM2_HIP(vals_in.alloc(total));
-    CM2_HIP(cm2::dev_malloc(&f->d_win_k, sizeof(uint32_t) * total));
-    CM2_HIP(cm2::dev_malloc(&f->d_win_q, sizeof(uint16_t) * total));
-    k_win_keys<<<grid_for(total), kBlock, 0, st>>>(f->d_wins, f->nwin, d_idx, keys_in, vals_in);
-    CM2_LAUNCH_OK();
-    int end_bit = 33;
-    while (((int64_t)1 << (end_bit - 32)) <= f->nwin && end_bit < 64) ++end_bit;
-    size_t tb = 0;
-    CM2_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, keys_in.p, keys_out.p, vals_in.p,
-                                               f->d_win_q, total, 0, end_bit, st));
-    CM2_HIP(d_temp.alloc(tb + 16));
-    CM2_HIP(hipcub::DeviceRadixSort::SortPairs(d_temp.p, tb, keys_in.p, keys_out.p, vals_in.p,
-                                               f->d_win_q, total, 0, end_bit, st));
-    k_win_unpack<<<grid_for(total), kBlock, 0, st>>>(total, keys_out, f->d_win_k);
-    CM2_LAUNCH_OK();
-    CM2_HIP(hipStreamSynchronize(st));
+    auto keys = [&](uint64_t *k, uint16_t *v) {
+        k_win_keys<<<grid_for(f->nwin * kPermWin), kBlock, 0, st>>>(f->d_wins, f->nwin, d_idx, k, v);
+    };
+    if (int rc = window_lists(f->nwin, st, keys, &f->d_win_k, &f->d_win_q)) return rc;
     f->win_plan = plan_id;
     return 0;
 }
@@ -762,13 +723,12 @@ int filter_windows_build(cm2_filter *f, const uint32_t *d_idx, uint64_t plan_id,
 template <int K>
 int launch_windows(const cm2_filter *f, const double *d_in, double *d_out, hipStream_t st)
 {
-    constexpr size_t lds = sizeof(double) * kWinLen + kWinLen;
+    constexpr size_t lds = sizeof(double) * kPermWin + kPermWin;
     static size_t granted[64] = {0};
     CM2_HIP(ensure_dynamic_lds((const void *)k_filter_windows<K>, lds, granted));
-    const int grid = (int)(((f->nwin + 7) / 8) * 8);
-    k_filter_windows<K><<<grid, kWinT, lds, st>>>(f->d_wins, (int)f->nwin, f->d_start, f->d_len,
-                                                  f->d_kind, f->d_toff, f->d_table, f->d_coef,
-                                                  f->d_win_k, f->d_win_q, d_in, d_out);
+    k_filter_windows<K><<<window_grid(f->nwin), kPermT, lds, st>>>(
+        f->d_wins, (int)f->nwin, f->d_start, f->d_len, f->d_kind, f->d_toff, f->d_table, f->d_coef,
+        f->d_win_k, f->d_win_q, d_in, d_out);
     CM2_LAUNCH_OK();
     return 0;
 }

@@ -22,7 +22,7 @@
 // The two permutations are the plan's windowed ones (cm2_tiles.hip) with the flagged samples of a window, the
 // contiguous compact range [c_w, c_{w+1}), written into / read out of the LDS window beside the valid ones.
 #include "cm2_common.h"
-#include "cm2_tiles.h"
+#include "cm2_perm_window.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -213,8 +213,8 @@ __global__ __launch_bounds__(256) void k_gap_compare(int64_t nt, const void *__r
                                                       uint32_t *__restrict__ first)
 {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nt; i += stride)
-        if ((tb_dst[i] == kInvalidSample) != is_flagged<KIND>(flags, i)) atomicMin(first, (uint32_t)i);
+    flag_mismatch((int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride, nt, flags, tb_dst, first,
+                  [](const void *__restrict__ f, int64_t i) { return is_flagged<KIND>(f, i); });
 }
 
 // cw[w] = number of flagged samples before window w (lower_bound of w kPermWin in pos), w = 0 .. nwin
@@ -233,7 +233,7 @@ __global__ __launch_bounds__(256) void k_gap_window_table(int64_t nwin, int64_t 
     }
 }
 
-// k_perm_windows (cm2_tiles.hip) with the flagged samples merged in.  TO_TIME: out[t] = in[tile position of t] on
+// k_perm_windows (cm2_tiles.hip; the pieces: cm2_perm_window.h) with the flagged samples merged in.  TO_TIME: out[t] = in[tile position of t] on
 // the valid samples and gc[c] at the c-th flagged one -- every slot of a window below its span is one or the
 // other, so nothing is zero-filled (slots from span up are never read).  To tiles: out[tile position] = in[t] and
 // gc[c] = in[pos[c]].  The flagged samples of window w are pos[cw[w] .. cw[w + 1]), read coalesced.
@@ -248,36 +248,25 @@ __global__ __launch_bounds__(kPermT) void k_gap_perm_windows(int64_t nt, int64_t
                                                               double *__restrict__ gc_out)
 {
     __shared__ double win[kPermWin];
-    const int per_xcd = (int)((nwin + 7) / 8);
-    const int64_t w = (int64_t)(blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
+    const int64_t w = window_of_workgroup(nwin);
     if (w >= nwin) return;
-    const int64_t t0 = w * kPermWin, base = w * kPermWin;
-    const int span = (int)((nt - t0 < kPermWin) ? nt - t0 : kPermWin);
+    const int64_t t0 = w * kPermWin;
+    const int span = (int)window_span(nt, t0);
     const int t = threadIdx.x;
     const uint32_t c0 = cw[w], c1 = cw[w + 1];
-    uint32_t kk[kPermPer];
-    uint16_t qq[kPermPer];
-#pragma unroll
-    for (int u = 0; u < kPermPer; ++u) {
-        kk[u] = lst_k[base + t + u * kPermT];
-        qq[u] = lst_q[base + t + u * kPermT];
-    }
+    WindowEntries e;
+    e.load(lst_k, lst_q, w);
     if (TO_TIME) {
         double vv[kPermPer];
-#pragma unroll
-        for (int u = 0; u < kPermPer; ++u) vv[u] = (kk[u] != kInvalidSample) ? in[kk[u]] : 0.0;
-#pragma unroll
-        for (int u = 0; u < kPermPer; ++u)
-            if (kk[u] != kInvalidSample) win[qq[u]] = vv[u];
+        e.gather(in, vv);
+        e.each_valid([&](int u, uint32_t, uint16_t q) { win[q] = vv[u]; });
         for (uint32_t c = c0 + t; c < c1; c += kPermT) win[(int64_t)pos[c] - t0] = gc_in[c];
         __syncthreads();
         for (int j = t; j < span; j += kPermT) out[t0 + j] = win[j];
     } else {
         for (int j = t; j < span; j += kPermT) win[j] = in[t0 + j];
         __syncthreads();
-#pragma unroll
-        for (int u = 0; u < kPermPer; ++u)
-            if (kk[u] != kInvalidSample) out[kk[u]] = win[qq[u]];
+        e.each_valid([&](int, uint32_t k, uint16_t q) { out[k] = win[q]; });
         for (uint32_t c = c0 + t; c < c1; c += kPermT) gc_out[c] = win[(int64_t)pos[c] - t0];
     }
 }
@@ -607,16 +596,14 @@ extern "C" int cm2_gaps_prepare_tiles(cm2_gaps *g, const cm2_tiles *tiles, void 
               "%lld, the gaps flag %lld: not the same pointing", (long long)tiles->nvalid, (long long)g->nt,
               (long long)g->ng);
     hipStream_t stream = as_stream(stream_);
-    DevTemp<uint32_t> d_first;
-    CM2_HIP(d_first.alloc(1));
-    CM2_HIP(hipMemsetAsync(d_first.p, 0xFF, sizeof(uint32_t), stream));
-    if (g->kind == 0)
-        k_gap_compare<0><<<grid_for(g->nt), kBlock, 0, stream>>>(g->nt, g->d_flags, tiles->d_tb_dst, d_first.p);
-    else
-        k_gap_compare<1><<<grid_for(g->nt), kBlock, 0, stream>>>(g->nt, g->d_flags, tiles->d_tb_dst, d_first.p);
-    CM2_LAUNCH_OK();
     uint32_t first = 0;
-    CM2_HIP(cm2::download(&first, d_first.p, sizeof(first), stream));
+    auto compare = [&](uint32_t *d_first) {
+        if (g->kind == 0)
+            k_gap_compare<0><<<grid_for(g->nt), kBlock, 0, stream>>>(g->nt, g->d_flags, tiles->d_tb_dst, d_first);
+        else
+            k_gap_compare<1><<<grid_for(g->nt), kBlock, 0, stream>>>(g->nt, g->d_flags, tiles->d_tb_dst, d_first);
+    };
+    if (int rc = cm2::first_flag_mismatch(stream, compare, &first)) return rc;
     CM2_CHECK(first == kInvalidSample, "cm2_gaps_prepare_tiles: both flag %lld samples, but sample %u is flagged in "
               "one and valid in the other: not the same pointing", (long long)g->ng, first);
     bool windows = false;
@@ -664,8 +651,7 @@ extern "C" int cm2_gaps_tiles_to_time(const cm2_gaps *g, const cm2_tiles *tiles,
         if (int rc = cm2_tod_tiles_to_time(tiles, d_tb, d_time, stream_)) return rc;
         return cm2_gaps_scatter(g, d_compact, d_time, stream_);
     }
-    const int grid = (int)(((g->nwin + 7) / 8) * 8);
-    k_gap_perm_windows<true><<<grid, kPermT, 0, as_stream(stream_)>>>(
+    k_gap_perm_windows<true><<<window_grid(g->nwin), kPermT, 0, as_stream(stream_)>>>(
         g->nt, g->nwin, tiles->d_perm_k, tiles->d_perm_q, g->d_pos, g->d_win_c, d_tb, d_time, d_compact, nullptr);
     CM2_LAUNCH_OK();
     return 0;
@@ -681,8 +667,7 @@ extern "C" int cm2_gaps_time_to_tiles(const cm2_gaps *g, const cm2_tiles *tiles,
         if (int rc = cm2_gaps_gather(g, d_time, d_compact_out, stream_)) return rc;
         return cm2_tod_time_to_tiles(tiles, d_time, d_tb, stream_);
     }
-    const int grid = (int)(((g->nwin + 7) / 8) * 8);
-    k_gap_perm_windows<false><<<grid, kPermT, 0, as_stream(stream_)>>>(
+    k_gap_perm_windows<false><<<window_grid(g->nwin), kPermT, 0, as_stream(stream_)>>>(
         g->nt, g->nwin, tiles->d_perm_k, tiles->d_perm_q, g->d_pos, g->d_win_c, d_time, d_tb, nullptr,
         d_compact_out);
     CM2_LAUNCH_OK();

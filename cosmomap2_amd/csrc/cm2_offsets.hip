@@ -21,13 +21,13 @@
 // ascending window order.  The time-order and the tile-order form differ only in how the window reaches LDS, so
 // they give the same bits.
 //
-// Tile-order forms work on the plan's windowed permutation lists (cm2_tiles.h): to tiles, a thread takes its list
+// Tile-order forms work on the plan's windowed permutation lists (cm2_perm_window.h): to tiles, a thread takes its list
 // entries (k, q), finds the baseline of sample t0 + q and stores w_b a_j at tile position k; from tiles, the window
 // is gathered as k_perm_windows<true> does.  A stream shorter than one window has no lists: the time-order kernel
 // and the plan's per-sample permutation serve.
 #include "cm2_common.h"
 #include "cm2_offsets_policy.h"
-#include "cm2_tiles.h"
+#include "cm2_perm_window.h"
 
 #include <cmath>
 #include <vector>
@@ -48,13 +48,6 @@ struct Table {
     const double *w;        // [nb] weights, nullptr: 1
     int64_t nb, L, nt;
 };
-
-// window of the workgroup: consecutive windows go to the same XCD (as k_perm_windows)
-__device__ __forceinline__ int64_t window_of_workgroup(int64_t nwin)
-{
-    const int per_xcd = (int)((nwin + 7) / 8);
-    return (int64_t)(blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
-}
 
 __device__ __forceinline__ void emit(const Table &T, int64_t t0, int64_t w, const of::Baseline &s, double total,
                                      double *__restrict__ out, double *__restrict__ side)
@@ -156,7 +149,7 @@ __device__ __forceinline__ void offsets_time(const Table &T, int64_t nwin, const
     const int64_t w = window_of_workgroup(nwin);
     if (w >= nwin) return;
     const int64_t t0 = w * of::kWin;
-    const int span = (int)((T.nt - t0 < of::kWin) ? T.nt - t0 : of::kWin);
+    const int span = (int)window_span(T.nt, t0);
     if ((int)threadIdx.x >= span) return;
     int64_t b = of::block_of(T.off, T.nb, t0 + threadIdx.x);
     for (int i = threadIdx.x; i < span; i += kPermT) {
@@ -195,7 +188,7 @@ __global__ __launch_bounds__(kPermT) void k_offsets_sum(Table T, int64_t nwin, c
     const int64_t w = window_of_workgroup(nwin);
     if (w >= nwin) return;
     const int64_t t0 = w * of::kWin;
-    const int span = (int)((T.nt - t0 < of::kWin) ? T.nt - t0 : of::kWin);
+    const int span = (int)window_span(T.nt, t0);
     for (int i = threadIdx.x; i < span; i += kPermT) {
         const double v = y[t0 + i];
         win[of::pad(i)] = pix[t0 + i] >= 0 ? v : 0.0;
@@ -215,24 +208,20 @@ __global__ __launch_bounds__(kPermT) void k_offsets_from_tiles(Table T, int64_t 
     int *sf = reinterpret_cast<int *>(sv + of::kChunks);
     const int64_t w = window_of_workgroup(nwin);
     if (w >= nwin) return;
-    const int64_t t0 = w * of::kWin, base = w * of::kWin;
-    const int span = (int)((T.nt - t0 < of::kWin) ? T.nt - t0 : of::kWin);
+    const int64_t t0 = w * of::kWin;
+    const int span = (int)window_span(T.nt, t0);
     const int t = threadIdx.x;
-    uint32_t kk[kPermPer];
-    uint16_t qq[kPermPer];
-#pragma unroll
-    for (int u = 0; u < kPermPer; ++u) {
-        kk[u] = lst_k[base + t + u * kPermT];
-        qq[u] = lst_q[base + t + u * kPermT];
-    }
+    WindowEntries e;
+    e.load(lst_k, lst_q, w);
     double vv[kPermPer];
-#pragma unroll
-    for (int u = 0; u < kPermPer; ++u) vv[u] = (kk[u] != kInvalidSample) ? tb[kk[u]] : 0.0;
+    e.gather(tb, vv);
     for (int i = t; i < span; i += kPermT) win[of::pad(i)] = 0.0;      // flagged samples count as 0
     __syncthreads();
+    // (not through each_valid: with the span guard inside a callable the compiler commutes the 32 compares and the
+    // kernel no longer is the instruction stream it was)
 #pragma unroll
     for (int u = 0; u < kPermPer; ++u)
-        if (kk[u] != kInvalidSample && (int)qq[u] < span) win[of::pad(qq[u])] = vv[u];
+        if (e.k[u] != kInvalidSample && (int)e.q[u] < span) win[of::pad(e.q[u])] = vv[u];
     __syncthreads();
     window_sums(T, w, span, win, sv, sf, out, side);
 }
@@ -281,8 +270,8 @@ __global__ __launch_bounds__(256) void k_offsets_compare(int64_t nt, const int32
                                                           uint32_t *__restrict__ first)
 {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nt; i += stride)
-        if ((tb_dst[i] == kInvalidSample) != (pix[i] < 0)) atomicMin(first, (uint32_t)i);
+    flag_mismatch((int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride, nt, pix, tb_dst, first,
+                  [](const int32_t *__restrict__ p, int64_t i) { return p[i] < 0; });
 }
 
 }  // namespace
@@ -307,8 +296,6 @@ static Table table_of(const cm2_offsets *f, bool weighted)
 {
     return Table{f->d_off, f->d_j0, weighted ? f->d_w : nullptr, f->nb, f->Lc, f->nt};
 }
-
-static int window_grid(int64_t nwin) { return (int)(((nwin + 7) / 8) * 8); }
 
 extern "C" int cm2_offsets_destroy(cm2_offsets *f)
 {
@@ -475,13 +462,11 @@ extern "C" int cm2_offsets_prepare_tiles(cm2_offsets *f, const cm2_tiles *tiles,
               "the offsets count %lld: not the same pointing", (long long)tiles->nvalid, (long long)f->nt,
               (long long)f->nvalid);
     hipStream_t stream = as_stream(stream_);
-    DevTemp<uint32_t> d_first;
-    CM2_HIP(d_first.alloc(1));
-    CM2_HIP(hipMemsetAsync(d_first.p, 0xFF, sizeof(uint32_t), stream));
-    k_offsets_compare<<<grid_for(f->nt), kBlock, 0, stream>>>(f->nt, f->d_pix, tiles->d_tb_dst, d_first.p);
-    CM2_LAUNCH_OK();
     uint32_t first = 0;
-    CM2_HIP(cm2::download(&first, d_first.p, sizeof(first), stream));
+    auto compare = [&](uint32_t *d_first) {
+        k_offsets_compare<<<grid_for(f->nt), kBlock, 0, stream>>>(f->nt, f->d_pix, tiles->d_tb_dst, d_first);
+    };
+    if (int rc = cm2::first_flag_mismatch(stream, compare, &first)) return rc;
     CM2_CHECK(first == kInvalidSample, "cm2_offsets_prepare_tiles: both have %lld valid samples, but sample %u is "
               "flagged in one and valid in the other: not the same pointing", (long long)f->nvalid, first);
     bool windows = false;

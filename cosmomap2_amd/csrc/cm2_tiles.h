@@ -6,6 +6,7 @@
 #include "cm2_pixindex.h"
 #include "cm2_plan_policy.h"
 
+#include <functional>
 #include <vector>
 
 namespace cm2 {
@@ -158,11 +159,23 @@ void fx_free(cm2_tiles *t);
 int64_t fx_designed_bytes(const cm2_tiles *t);
 int fx_parts_info(const cm2_tiles *t, int64_t *h_info);   // cm2_tiles_pt_parts
 
-// Windowed permutations between time and tile order (cm2_tiles.hip; the forms that merge the flagged samples in:
-// cm2_gaps.hip): a workgroup of kPermT threads owns kPermWin consecutive time samples.  perm_lists builds the
-// plan's address-sorted lists d_perm_k / d_perm_q on first use (allocates, synchronises); *use = false for a
-// TOD shorter than one window, which keeps the per-sample kernels.
+// Windowed exchange between time and tile order: a workgroup of kPermT threads owns kPermWin consecutive time
+// samples and reaches their tile-order positions through an address-sorted list.  The list format and the device
+// pieces that read it: cm2_perm_window.h.  perm_lists builds the plan's lists d_perm_k / d_perm_q on first use
+// (allocates, synchronises); *use = false for a TOD shorter than one window, which keeps the per-sample kernels.
 constexpr int kPermWin = 8192, kPermT = 256, kPermPer = kPermWin / kPermT;
 int perm_lists(const cm2_tiles *t, hipStream_t st, bool *use);
+
+// The builder of window lists (cm2_tiles.hip).  fill_keys launches the caller's kernel that writes, for every slot
+// g < nwin kPermWin, keys[g] = (window << 32) | tile-order position (kInvalidSample: none) and vals[g] = offset in
+// the window; the slots are sorted by key and come back as *lst_k (the keys' low words) and *lst_q, which the caller
+// owns.  Synchronises; on failure nothing is left allocated.
+int window_lists(int64_t nwin, hipStream_t st, const std::function<void(uint64_t *keys, uint16_t *vals)> &fill_keys,
+                 uint32_t **lst_k, uint16_t **lst_q);
+
+// "Does this handle flag the same samples as the plan?"  launch_compare launches the caller's kernel around
+// flag_mismatch (cm2_perm_window.h) on the word it is given; *first = the smallest sample whose flag differs,
+// kInvalidSample when there is none.
+int first_flag_mismatch(hipStream_t st, const std::function<void(uint32_t *d_first)> &launch_compare, uint32_t *first);
 }  // namespace cm2
 

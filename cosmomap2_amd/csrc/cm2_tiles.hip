@@ -30,7 +30,7 @@
 //
 // Reference loops replaced: interfaces/linearoperators.py:483-489 (mult_iqu) and :509-516
 // (rmult_iqu) and their I / QU variants.
-#include "cm2_tiles.h"
+#include "cm2_perm_window.h"
 
 #include <hipcub/hipcub.hpp>
 #include <cstring>
@@ -539,7 +539,8 @@ __global__ __launch_bounds__(1024) void k_tiles_to_time(int64_t nt, int64_t chun
 // payload.  Here a workgroup owns kPermWin consecutive time samples, reaches their TB
 // positions through a list sorted by address (one contiguous run per tile) and stages the
 // window in LDS, so that both sides of the copy are streams: 6 + 8 + 8 bytes per sample.
-// (kPermWin, kPermT, kPermPer: cm2_tiles.h -- cm2_gaps.hip builds its merging forms on the same lists)
+// (the list format and the pieces the kernel is made of: cm2_perm_window.h, shared with cm2_gaps.hip,
+// cm2_offsets.hip and cm2_filter.hip)
 
 template <bool TO_TIME>
 __global__ __launch_bounds__(kPermT) void k_perm_windows(int64_t nt, int64_t nwin,
@@ -549,36 +550,25 @@ __global__ __launch_bounds__(kPermT) void k_perm_windows(int64_t nt, int64_t nwi
                                                           double *__restrict__ out)
 {
     __shared__ double win[kPermWin];
-    const int per_xcd = (int)((nwin + 7) / 8);
-    const int64_t w = (int64_t)(blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
+    const int64_t w = window_of_workgroup(nwin);
     if (w >= nwin) return;
-    const int64_t t0 = w * kPermWin, base = w * kPermWin;
-    const int span = (int)((nt - t0 < kPermWin) ? nt - t0 : kPermWin);
+    const int64_t t0 = w * kPermWin;
+    const int span = (int)window_span(nt, t0);
     const int t = threadIdx.x;
-    uint32_t kk[kPermPer];
-    uint16_t qq[kPermPer];
-#pragma unroll
-    for (int u = 0; u < kPermPer; ++u) {
-        kk[u] = lst_k[base + t + u * kPermT];
-        qq[u] = lst_q[base + t + u * kPermT];
-    }
+    WindowEntries e;
+    e.load(lst_k, lst_q, w);
     if (TO_TIME) {
         double vv[kPermPer];
-#pragma unroll
-        for (int u = 0; u < kPermPer; ++u) vv[u] = (kk[u] != kInvalidSample) ? in[kk[u]] : 0.0;
+        e.gather(in, vv);
         for (int j = t; j < span; j += kPermT) win[j] = 0.0;      // flagged samples read as 0
         __syncthreads();
-#pragma unroll
-        for (int u = 0; u < kPermPer; ++u)
-            if (kk[u] != kInvalidSample) win[qq[u]] = vv[u];
+        e.each_valid([&](int u, uint32_t, uint16_t q) { win[q] = vv[u]; });
         __syncthreads();
         for (int j = t; j < span; j += kPermT) out[t0 + j] = win[j];
     } else {
         for (int j = t; j < span; j += kPermT) win[j] = in[t0 + j];
         __syncthreads();
-#pragma unroll
-        for (int u = 0; u < kPermPer; ++u)
-            if (kk[u] != kInvalidSample) out[kk[u]] = win[qq[u]];
+        e.each_valid([&](int, uint32_t k, uint16_t q) { out[k] = win[q]; });
     }
 }
 
@@ -1064,6 +1054,52 @@ static inline void perm_geometry(int64_t nt, int &blocks, int64_t &chunk)
     if (blocks < 1) blocks = 1;
 }
 
+// the one builder of window lists (cm2_tiles.h): keys by the caller's kernel, a radix sort over the window bits and
+// the 32 address bits, the low words unpacked
+int cm2::window_lists(int64_t nwin, hipStream_t st,
+                      const std::function<void(uint64_t *keys, uint16_t *vals)> &fill_keys, uint32_t **lst_k,
+                      uint16_t **lst_q)
+{
+    const int64_t total = nwin * kPermWin;
+    DevTemp<uint64_t> keys_in, keys_out;
+    DevTemp<uint16_t> vals_in, lq;
+    DevTemp<uint32_t> lk;
+    DevTemp<char> d_temp;
+    CM2_HIP(keys_in.alloc(total));
+    CM2_HIP(keys_out.alloc(total));
+    CM2_HIP(vals_in.alloc(total));
+    CM2_HIP(lk.alloc(total));
+    CM2_HIP(lq.alloc(total));
+    fill_keys(keys_in, vals_in);
+    CM2_LAUNCH_OK();
+    int end_bit = 33;
+    while (((int64_t)1 << (end_bit - 32)) <= nwin && end_bit < 64) ++end_bit;
+    size_t tb = 0;
+    CM2_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, keys_in.p, keys_out.p, vals_in.p, lq.p, total, 0,
+                                               end_bit, st));
+    CM2_HIP(d_temp.alloc(tb + 16));
+    CM2_HIP(hipcub::DeviceRadixSort::SortPairs(d_temp.p, tb, keys_in.p, keys_out.p, vals_in.p, lq.p, total, 0,
+                                               end_bit, st));
+    k_perm_unpack<<<grid_for(total), kBlock, 0, st>>>(total, keys_out, lk);
+    CM2_LAUNCH_OK();
+    CM2_HIP(hipStreamSynchronize(st));
+    *lst_k = lk.keep();
+    *lst_q = lq.keep();
+    return 0;
+}
+
+int cm2::first_flag_mismatch(hipStream_t st, const std::function<void(uint32_t *d_first)> &launch_compare,
+                             uint32_t *first)
+{
+    DevTemp<uint32_t> d_first;
+    CM2_HIP(d_first.alloc(1));
+    CM2_HIP(hipMemsetAsync(d_first.p, 0xFF, sizeof(uint32_t), st));
+    launch_compare(d_first);
+    CM2_LAUNCH_OK();
+    CM2_HIP(cm2::download(first, d_first.p, sizeof(*first), st));
+    return 0;
+}
+
 // lists of the windowed permutations (a TOD shorter than one window keeps the per-sample kernels)
 int cm2::perm_lists(const cm2_tiles *tc, hipStream_t st, bool *use)
 {
@@ -1071,36 +1107,11 @@ int cm2::perm_lists(const cm2_tiles *tc, hipStream_t st, bool *use)
     *use = false;
     if (t->nt < kPermWin) return 0;
     if (!t->d_perm_k) {
-        const int64_t nwin = (t->nt + kPermWin - 1) / kPermWin, total = nwin * kPermWin;
-        DevTemp<uint64_t> keys_in, keys_out;
-        DevTemp<uint16_t> vals_in;
-        DevTemp<char> d_temp;
-        CM2_HIP(keys_in.alloc(total));
-        CM2_HIP(keys_out.alloc(total));
-        CM2_HIP(vals_in.alloc(total));
-        uint32_t *lk = nullptr;
-        uint16_t *lq = nullptr;
-        CM2_HIP(cm2::dev_malloc(&lk, sizeof(uint32_t) * total));
-        DevTemp<uint32_t> guard_k;
-        guard_k.p = lk;
-        CM2_HIP(cm2::dev_malloc(&lq, sizeof(uint16_t) * total));
-        DevTemp<uint16_t> guard_q;
-        guard_q.p = lq;
-        k_perm_keys<<<grid_for(total), kBlock, 0, st>>>(t->nt, nwin, t->d_tb_dst, keys_in, vals_in);
-        CM2_LAUNCH_OK();
-        int end_bit = 33;
-        while (((int64_t)1 << (end_bit - 32)) <= nwin && end_bit < 64) ++end_bit;
-        size_t tb = 0;
-        CM2_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, keys_in.p, keys_out.p, vals_in.p, lq,
-                                                   total, 0, end_bit, st));
-        CM2_HIP(d_temp.alloc(tb + 16));
-        CM2_HIP(hipcub::DeviceRadixSort::SortPairs(d_temp.p, tb, keys_in.p, keys_out.p, vals_in.p, lq,
-                                                   total, 0, end_bit, st));
-        k_perm_unpack<<<grid_for(total), kBlock, 0, st>>>(total, keys_out, lk);
-        CM2_LAUNCH_OK();
-        CM2_HIP(hipStreamSynchronize(st));
-        t->d_perm_k = guard_k.keep();
-        t->d_perm_q = guard_q.keep();
+        const int64_t nwin = (t->nt + kPermWin - 1) / kPermWin;
+        auto keys = [&](uint64_t *k, uint16_t *v) {
+            k_perm_keys<<<grid_for(nwin * kPermWin), kBlock, 0, st>>>(t->nt, nwin, t->d_tb_dst, k, v);
+        };
+        if (int rc = window_lists(nwin, st, keys, &t->d_perm_k, &t->d_perm_q)) return rc;
         t->nperm_win = nwin;
     }
     *use = true;
@@ -1114,9 +1125,8 @@ extern "C" int cm2_tod_time_to_tiles(const cm2_tiles *t, const double *d_time, d
     bool windows = false;
     if (int rc = perm_lists(t, as_stream(stream_), &windows)) return rc;
     if (windows) {
-        const int grid = (int)(((t->nperm_win + 7) / 8) * 8);
-        k_perm_windows<false><<<grid, kPermT, 0, as_stream(stream_)>>>(t->nt, t->nperm_win, t->d_perm_k,
-                                                                      t->d_perm_q, d_time, d_tb);
+        k_perm_windows<false><<<window_grid(t->nperm_win), kPermT, 0, as_stream(stream_)>>>(
+            t->nt, t->nperm_win, t->d_perm_k, t->d_perm_q, d_time, d_tb);
         CM2_LAUNCH_OK();
         return 0;
     }
@@ -1135,9 +1145,8 @@ extern "C" int cm2_tod_tiles_to_time(const cm2_tiles *t, const double *d_tb, dou
     bool windows = false;
     if (int rc = perm_lists(t, as_stream(stream_), &windows)) return rc;
     if (windows) {
-        const int grid = (int)(((t->nperm_win + 7) / 8) * 8);
-        k_perm_windows<true><<<grid, kPermT, 0, as_stream(stream_)>>>(t->nt, t->nperm_win, t->d_perm_k,
-                                                                     t->d_perm_q, d_tb, d_time);
+        k_perm_windows<true><<<window_grid(t->nperm_win), kPermT, 0, as_stream(stream_)>>>(
+            t->nt, t->nperm_win, t->d_perm_k, t->d_perm_q, d_tb, d_time);
         CM2_LAUNCH_OK();
         return 0;
     }

@@ -966,6 +966,18 @@ class _FilterHandle(object):
             self.h = None
 
 
+def _flags_match(op, P):
+    """The tile order has no slot for the samples ``P`` flags; a time-domain operator may run there only
+    if it flags exactly the same samples (the reference passes ``P.pairs``).  Cached on ``op`` per ``P``."""
+    cache = op.__dict__.get("_flag_match")
+    if cache is None or cache[0]() is not P:          # weak reference: an id() can be reused
+        a, b = op._d_pix, P._d_pix
+        ok = a.numel() == b.numel() and (
+            a.data_ptr() == b.data_ptr() or bool(torch.equal(a < 0, b < 0)))
+        cache = op._flag_match = (weakref.ref(P), ok)
+    return cache[1]
+
+
 class FilterLO(_DeviceOp):
     """
     Sub-scan filter of a time stream (reference: linearoperators.py:94-283).
@@ -1066,15 +1078,7 @@ class FilterLO(_DeviceOp):
         return self._apply(self.poly_order, d)
 
     def _tile_compatible(self, P):
-        """The tile order has no slot for the samples ``P`` flags; the filter may run there only
-        if it flags exactly the same samples (the reference passes ``P.pairs``)."""
-        cache = self.__dict__.get("_flag_match")
-        if cache is None or cache[0]() is not P:          # weak reference: an id() can be reused
-            a, b = self._d_pix, P._d_pix
-            ok = a.numel() == b.numel() and (
-                a.data_ptr() == b.data_ptr() or bool(torch.equal(a < 0, b < 0)))
-            cache = self._flag_match = (weakref.ref(P), ok)
-        return cache[1]
+        return _flags_match(self, P)
 
     def _apply_tiles(self, T, d_in_tb, d_out_tb):
         """Filter a TOD held in the tile-bucketed order ``T``; False if the chunks do not fit
@@ -1334,12 +1338,4 @@ class HWPSSFilterLO(_DeviceOp):
         return c, s
 
     def _tile_compatible(self, P):
-        """As for :class:`FilterLO`: the tile order has no slot for the samples ``P`` flags, so the filter may
-        stand between tile-order ``P`` and ``P^T`` only if it flags exactly the same samples."""
-        cache = self.__dict__.get("_flag_match")
-        if cache is None or cache[0]() is not P:
-            a, b = self._d_pix, P._d_pix
-            ok = a.numel() == b.numel() and (
-                a.data_ptr() == b.data_ptr() or bool(torch.equal(a < 0, b < 0)))
-            cache = self._flag_match = (weakref.ref(P), ok)
-        return cache[1]
+        return _flags_match(self, P)

@@ -40,7 +40,7 @@ LD, U53, _ld = V.LD, V.U53, V._ld
 bits, assert_bit_equal = V.bits, V.assert_bit_equal
 
 KWAVE = 64
-WIN_LEN = 8192                       # kWinLen of cm2_filter.hip
+WIN_LEN = 8192                       # kPermWin of cm2_tiles.h
 REG_SMALL, REG_LARGE = 512, 2048     # kWave * kRegSmall, kWave * kRegLarge
 
 MUTATIONS = ("drop_last", "j_le_n", "skip_stage", "kind_threshold", "table_neighbour",

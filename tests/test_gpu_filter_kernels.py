@@ -23,8 +23,8 @@ Kernels and the case that reaches them (to be kept in step with the dispatch cod
                           hipMemsetAsync (no chunk)     tests/test_gpu_parity.py
   cm2_filter_apply_tiles  filter_windows_build          test_tile_order: layouts a, b1, b7, b8, c0 .. c3
                                                         (tileable), d (a chunk of 8193 samples: not)
-                          k_win_keys, k_win_unpack      every tileable layout; rebuilt for another plan id
-                                                        in test_tile_order_second_plan
+                          k_win_keys, window_lists      every tileable layout; rebuilt for another plan id
+                          (cm2_tiles.hip)               in test_tile_order_second_plan
                           k_filter_windows<0,2..8>      test_tile_order[a-0..7]; nwin = 9 (16 workgroups,
                                                         7 exit), 1, 7, 8, 2
                           hipMemsetAsync (win_memset)   test_tile_order[c1|c2|c3-*]
