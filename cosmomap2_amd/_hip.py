@@ -157,6 +157,12 @@ PROTOTYPES = {
     "cm2_hwpss_apply": [_vp, _vp, _vp, _vp],
     "cm2_hwpss_fit": [_vp, _vp, _vp, _vp],
     "cm2_hwpss_tables": [_vp, _vp, _vp, _vp],
+    "cm2_cmode_create": [ctypes.POINTER(_vp), _i64, _int, _int, ctypes.POINTER(_i64), _int, _vp, _vp, _vp],
+    "cm2_cmode_destroy": [_vp],
+    "cm2_cmode_info": [_vp, ctypes.POINTER(_i64)],
+    "cm2_cmode_apply": [_vp, _vp, _vp, _vp],
+    "cm2_cmode_fit": [_vp, _vp, _vp, _vp],
+    "cm2_cmode_status": [_vp, _vp],
 }
 _RESTYPE = {"cm2_last_error": ctypes.c_char_p, "cm2_reduce_work_doubles": _i64,
             "cm2_gemm_tn_work_doubles": _i64}
@@ -213,8 +219,8 @@ ERR_OUT_OF_MEMORY = 3          # CM2_ERR_OUT_OF_MEMORY of include/cosmomap2.h
 # Entry points that may be called again after an out-of-memory failure: they build a new object (a failed
 # build frees what it had made) or overwrite their outputs from their inputs.  NOT in the list: the in-place
 # updates (cm2_axpy, cm2_scal, cm2_Z_axpy, cm2_panel_gemm with accumulate, cm2_pcg_update_*,
-# cm2_flag_samples, cm2_compact_*, cm2_noise_sim_draw with add), which a second run would apply twice, and the
-# drivers with callbacks (cm2_pcg, cm2_pcg_sharded, cm2_arnoldi).
+# cm2_flag_samples, cm2_compact_*, cm2_noise_sim_draw with add, cm2_cmode_apply whose output may be its input),
+# which a second run would apply twice, and the drivers with callbacks (cm2_pcg, cm2_pcg_sharded, cm2_arnoldi).
 RESTARTABLE = frozenset([
     "cm2_pointing_create", "cm2_pointing_build_sell", "cm2_pointing_set_weights",
     "cm2_P_apply", "cm2_Pt_apply", "cm2_PtNP_diag_apply",
@@ -238,6 +244,7 @@ RESTARTABLE = frozenset([
     "cm2_offsets_prepare_tiles", "cm2_offsets_to_tiles", "cm2_offsets_from_tiles",
     "cm2_offset_prior_from_psd", "cm2_pointing_expand",
     "cm2_hwpss_create", "cm2_hwpss_apply", "cm2_hwpss_fit", "cm2_hwpss_tables",
+    "cm2_cmode_create", "cm2_cmode_fit", "cm2_cmode_status",
 ])
 
 

@@ -1,0 +1,63 @@
+// cm2_cmode_policy.h -- the device-free arithmetic of the common-mode filter (cm2_cmode.hip): which arguments are
+// accepted and how the (group, time sample) units are laid over workgroups.  Plain C++: tests/test_cmode_cpu.py
+// compiles it with the host compiler and checks it against Python.
+//
+// The stream is ndet rows of ns samples.  Group g is the detectors [edges[g], edges[g + 1]),
+// 0 = edges[0] < ... < edges[ngroups] = ndet; unit (g, i) = sample i of group g has the index g ns + i.  One thread
+// per unit, kThreads threads a workgroup; a workgroup never crosses a group: group g owns the workgroups
+// [g B, (g + 1) B) with B = blocks_per_group(ns), and thread t of workgroup w takes the sample
+// (w - g B) kThreads + t of its group, or nothing when that is >= ns.
+#pragma once
+#include <cstdint>
+
+namespace cm2 {
+namespace cmode {
+
+constexpr int kThreads = 256;              // threads of a workgroup = units of a workgroup
+constexpr int kMaxK = 10;                  // templates per detector (the monomials of total degree <= 3)
+
+// the classes of a unit, as cm2_cmode_status reports them
+enum Class { kFitted = 0, kEmpty = 1, kFew = 2, kPivot = 3 };
+
+enum Status { kOk = 0, kBadK = 1, kBadSize = 2, kBadEdges = 3, kTooLarge = 4 };
+
+// (constexpr: callable from device code as well)
+constexpr int packed(int K) { return K * (K + 1) / 2; }                   // doubles of the lower triangle
+constexpr int packed_at(int i, int j) { return i * (i + 1) / 2 + j; }     // entry (i, j), j <= i
+constexpr int64_t blocks_per_group(int64_t ns) { return (ns + kThreads - 1) / kThreads; }
+
+struct Launch {
+    int64_t blocks_per_group = 0, blocks = 0, units = 0, nt = 0;
+};
+
+// fills *l; anything but kOk leaves it unspecified.  The limits keep every sample index (ndet ns <= 2^46) and every
+// coefficient index (ngroups K ns <= 10 x 2^46) below 2^63, and the workgroup count (a grid dimension) below 2^31.
+inline Status check(Launch *l, int64_t ns, int64_t ndet, int64_t ngroups, const int64_t *edges, int K)
+{
+    if (K < 1 || K > kMaxK) return kBadK;
+    if (ns < 1 || ndet < 1 || ngroups < 1 || !edges) return kBadSize;
+    if (ngroups > ndet) return kBadEdges;
+    if (edges[0] != 0 || edges[ngroups] != ndet) return kBadEdges;
+    for (int64_t g = 0; g < ngroups; ++g)
+        if (edges[g + 1] <= edges[g]) return kBadEdges;
+    const int64_t lim = (int64_t)1 << 31;
+    if (ndet >= lim) return kTooLarge;
+    if (ndet > (((int64_t)1 << 46) / ns)) return kTooLarge;
+    const int64_t b = blocks_per_group(ns);
+    if (ngroups > (lim - 1) / b) return kTooLarge;
+    l->blocks_per_group = b;
+    l->blocks = b * ngroups;
+    l->units = ngroups * ns;
+    l->nt = ndet * ns;
+    return kOk;
+}
+
+// workgroup w -> its group and the first sample of the group it covers
+inline void block_position(const Launch &l, int64_t w, int64_t *group, int64_t *first)
+{
+    *group = w / l.blocks_per_group;
+    *first = (w - *group * l.blocks_per_group) * kThreads;
+}
+
+}  // namespace cmode
+}  // namespace cm2

@@ -31,7 +31,7 @@ torch = D.torch
 __all__ = ["SparseLO", "ToeplitzLO", "BlockLO", "BlockDiagonalLO",
            "BlockDiagonalPreconditionerLO", "InverseLO", "CoarseLO", "DeflationLO",
            "TwoLevelPreconditionerLO", "FilterLO", "GroundFilterLO", "HWPSSFilterLO", "hwpss_plan",
-           "set_pointing_mode", "lp"]
+           "CommonModeFilterLO", "cmode_groups", "focalplane_modes", "set_pointing_mode", "lp"]
 
 _I64P = ctypes.POINTER(ctypes.c_int64)
 _DBLP = ctypes.POINTER(ctypes.c_double)
@@ -436,7 +436,8 @@ def _fuse_chain(chain):
                 i += 3
                 changed = True
                 continue
-            if i + 2 < n and chain[i + 2] is P and isinstance(chain[i + 1], (FilterLO, GroundFilterLO, HWPSSFilterLO)) \
+            if i + 2 < n and chain[i + 2] is P \
+                    and isinstance(chain[i + 1], (FilterLO, GroundFilterLO, HWPSSFilterLO, CommonModeFilterLO)) \
                     and _use_tiles(P) and chain[i + 1]._tile_compatible(P):
                 # A = P^T F P, the production operator: tile-order P / P^T around the
                 # time-order filter (two streaming permutations instead of the exact-order
@@ -1336,6 +1337,157 @@ class HWPSSFilterLO(_DeviceOp):
         c, s = D.empty(self.ns), D.empty(self.ns)
         _hip.call("cm2_hwpss_tables", self._handle.h, D.ptr(c), D.ptr(s), D.stream())
         return c, s
+
+    def _tile_compatible(self, P):
+        return _flags_match(self, P)
+
+
+# ========================================================== CommonModeFilterLO ===
+CMODE_MAX_K = 10             # CM2_CMODE_MAX_K of include/cosmomap2.h
+CMODE_MAX_ORDER = 3
+
+
+def cmode_groups(ndet, groups=None):
+    """Group edges ``0 = g_0 < ... < g_G = ndet`` of :class:`CommonModeFilterLO` (host only, no GPU).
+
+    ``groups=None``: one group of all detectors.  An int: groups of that many detectors, the last one smaller when
+    it does not divide ``ndet``.  A 1-D array: the edges themselves, checked."""
+    if int(ndet) != ndet or int(ndet) < 1:
+        raise ValueError("ndet must be a positive integer, got %r" % (ndet,))
+    ndet = int(ndet)
+    if groups is None:
+        return np.array([0, ndet], dtype=np.int64)
+    if np.ndim(groups) == 0:
+        n = int(groups)
+        if n < 1 or n != groups:
+            raise ValueError("the group size must be a positive integer, got %r" % (groups,))
+        return np.append(np.arange(0, ndet, n, dtype=np.int64), np.int64(ndet))
+    e = np.asarray(groups)
+    if e.ndim != 1 or e.size < 2 or not np.issubdtype(e.dtype, np.integer):
+        raise lp.ShapeError("group edges must be a 1-D integer array of at least two entries")
+    e = np.ascontiguousarray(e, dtype=np.int64)
+    if e[0] != 0 or e[-1] != ndet or np.any(np.diff(e) <= 0):
+        raise ValueError("group edges must ascend strictly from 0 to ndet=%d" % ndet)
+    return e
+
+
+def focalplane_modes(xy, order, groups=None):
+    """Templates ``[ndet, K]`` of :class:`CommonModeFilterLO` from the focal-plane positions ``xy[ndet, 2]`` (host,
+    NumPy): the monomials ``x^(d-j) y^j`` for ``d = 0..order``, ``j = 0..d`` -- ``1, x, y, x^2, x y, y^2, ...`` --
+    ``K = (order + 1)(order + 2) / 2 = 1, 3, 6, 10`` for ``order = 0..3``.  Per group (as :func:`cmode_groups` takes
+    them) ``x`` and ``y`` are first centred on the middle of their range and divided by half of it, so that they
+    fill ``[-1, 1]``; a coordinate that is the same for the whole group becomes 0.  Powers are repeated products."""
+    if int(order) != order or not 0 <= int(order) <= CMODE_MAX_ORDER:
+        raise ValueError("order must be an integer in [0, %d], got %r" % (CMODE_MAX_ORDER, order))
+    order = int(order)
+    xy = np.asarray(xy, dtype=np.float64)
+    if xy.ndim != 2 or xy.shape[1] != 2 or xy.shape[0] < 1:
+        raise lp.ShapeError("xy must be [ndet, 2] focal-plane positions")
+    if not np.isfinite(xy).all():
+        raise ValueError("focal-plane positions must be finite")
+    edges = cmode_groups(xy.shape[0], groups)
+    u = np.empty_like(xy)
+    for a, b in zip(edges[:-1], edges[1:]):
+        lo, hi = xy[a:b].min(axis=0), xy[a:b].max(axis=0)
+        mid, half = (hi + lo) / 2.0, (hi - lo) / 2.0
+        u[a:b] = np.where(half > 0, (xy[a:b] - mid) / np.where(half > 0, half, 1.0), 0.0)
+    pw = [[np.ones(xy.shape[0])], [np.ones(xy.shape[0])]]
+    for axis in (0, 1):
+        for _ in range(order):
+            pw[axis].append(pw[axis][-1] * u[:, axis])
+    cols = [pw[0][d - j] * pw[1][j] for d in range(order + 1) for j in range(d + 1)]
+    return np.ascontiguousarray(np.stack(cols, axis=1))
+
+
+class _CModeHandle(object):
+    def __init__(self, handle, keep):
+        self.h = handle
+        self.keep = keep                   # the flag tensor the C side borrows
+
+    def __del__(self):
+        if self.h:
+            try:
+                _hip.load().cm2_cmode_destroy(self.h)
+            except Exception:
+                pass
+            self.h = None
+
+
+class CommonModeFilterLO(_DeviceOp):
+    """
+    Common-mode filter: per group of detectors and time sample, fit ``K`` templates ``Phi[k, :]`` across the
+    unflagged detectors and subtract them (``M - M Phi G^-1 Phi^T M``, symmetric and idempotent;
+    include/cosmomap2.h, f2d).  No counterpart in the reference.
+
+    ``CommonModeFilterLO(pix_samples, ndet, modes=None, groups=None)``: ``pix_samples[ndet * ns]`` the pixel of
+    every sample in the detector-major layout of ``expand_pointing`` (< 0 = flagged; an HBM int32 tensor is
+    adopted, not copied, and must not change afterwards); ``modes`` ``None`` (ones: the plain common mode) or
+    ``[ndet, K]``, ``K <= 10``, e.g. the relative gains or :func:`focalplane_modes`; ``groups`` as
+    :func:`cmode_groups` takes them.  A unit (group x sample) with fewer than ``K`` unflagged detectors, or whose
+    templates are collinear on them (Cholesky pivot <= 2^-10 of its diagonal entry), is skipped: its output and its
+    coefficients are 0; ``filter_info()`` counts them and ``status()`` names them.  Flagged samples are 0 in the
+    output.
+    """
+    CLASSES = ("fitted", "empty", "few", "pivot")
+
+    def __init__(self, pix_samples, ndet, modes=None, groups=None):
+        self.edges = cmode_groups(ndet, groups)
+        self.ndet, self.ngroups = int(ndet), int(self.edges.size) - 1
+        size = lambda a: int(a.numel()) if D.is_tensor(a) else int(np.size(a))
+        if modes is None:
+            modes = np.ones((self.ndet, 1))
+        shape = tuple(modes.shape) if D.is_tensor(modes) else np.shape(modes)
+        if len(shape) != 2 or shape[0] != self.ndet:
+            raise lp.ShapeError("modes must be [ndet, K] = [%d, K], got %r" % (self.ndet, tuple(shape)))
+        if not 1 <= shape[1] <= CMODE_MAX_K:
+            raise ValueError("modes has K = %d templates, K must be in [1, %d]" % (shape[1], CMODE_MAX_K))
+        self.K = int(shape[1])
+        n = size(pix_samples)
+        if n < self.ndet or n % self.ndet:
+            raise lp.ShapeError("pix_samples has %d entries, not a positive multiple of ndet = %d" % (n, self.ndet))
+        self.n, self.ns = n, n // self.ndet
+        D.require_gpu()
+        self._d_pix = D.i32(pix_samples).reshape(-1)
+        d_modes = D.f64(modes).reshape(-1)
+        handle = ctypes.c_void_p()
+        _hip.call("cm2_cmode_create", ctypes.byref(handle), self.ns, self.ndet, self.ngroups,
+                  self.edges.ctypes.data_as(_I64P), self.K, D.ptr(d_modes), D.ptr(self._d_pix), D.stream())
+        self._handle = _CModeHandle(handle, self._d_pix)
+        super(CommonModeFilterLO, self).__init__(nargin=self.n, nargout=self.n, matvec=self.mult, symmetric=True)
+
+    def filter_info(self):
+        info = (ctypes.c_int64 * 8)()
+        _hip.call("cm2_cmode_info", self._handle.h, info)
+        return dict(zip(("ns", "ndet", "ngroups", "K") + self.CLASSES, [int(v) for v in info]))
+
+    def _input(self, d):
+        x = D.f64(d)
+        if x.numel() != self.n:
+            raise lp.ShapeError("time-domain vector has %d entries, expected %d" % (x.numel(), self.n))
+        return x
+
+    def mult(self, d):
+        x = self._input(d)
+        out = D.empty(self.n)
+        _hip.call("cm2_cmode_apply", self._handle.h, D.ptr(x), D.ptr(out), D.stream())
+        return D.like_input(out, d)
+
+    _apply_all = mult
+
+    def coefficients(self, d):
+        """The fitted coefficients ``[ngroups, K, ns]`` of ``d`` (zeros for a skipped unit); nothing is
+        subtracted."""
+        x = self._input(d)
+        out = D.empty(self.ngroups * self.K * self.ns)
+        _hip.call("cm2_cmode_fit", self._handle.h, D.ptr(x), D.ptr(out), D.stream())
+        return D.like_input(out, d).reshape(self.ngroups, self.K, self.ns)
+
+    def status(self):
+        """The class of every unit, ``[ngroups, ns]`` uint8 on the host: 0 fitted, 1 empty (no unflagged
+        detector), 2 few (fewer than ``K``), 3 pivot (collinear templates)."""
+        out = D.empty(self.ngroups * self.ns, torch.uint8)
+        _hip.call("cm2_cmode_status", self._handle.h, D.ptr(out))
+        return D.to_host(out).reshape(self.ngroups, self.ns)
 
     def _tile_compatible(self, P):
         return _flags_match(self, P)

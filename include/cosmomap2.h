@@ -604,6 +604,65 @@ int cm2_hwpss_apply(cm2_hwpss *h, const double *d_in, double *d_out, void *strea
 int cm2_hwpss_fit(cm2_hwpss *h, const double *d_in, double *d_coeff, void *stream);
 int cm2_hwpss_tables(const cm2_hwpss *h, double *d_cos, double *d_sin, void *stream);
 
+/* ---- f2d: common-mode filter  (CommonModeFilterLO) ------------------------------------------
+ * Fits and removes focal-plane modes across the detectors, per group of detectors and time sample: the common mode
+ * of a wafer, its gradient and curvature over the focal plane.  No counterpart in the reference: the definition is
+ * the one below.
+ * Layout as cm2_pointing_expand writes it: nt = ndet ns, sample i of detector k at k ns + i, flagged where
+ * d_pix[nt] < 0.  The group edges 0 = g_0 < g_1 < ... < g_G = ndet cut the detectors into G contiguous groups (wafers,
+ * frequency bands).  Every detector carries K template values Phi[k, 0..K-1], 1 <= K <= CM2_CMODE_MAX_K,
+ * d_modes[k K + j]; they do not depend on time.  A unit is one (group, time sample) pair, unit g ns + i.
+ * Per unit, V the unflagged detectors of the group at sample i and m = |V|:
+ *     G = sum_{k in V} Phi_k Phi_k^T,   b = sum_{k in V} Phi_k v[k, i],   c = G^-1 b,
+ *     out[k, i] = v[k, i] - Phi_k^T c on V,  out[k, i] = 0 on the flagged samples of the unit
+ * (M - M Phi G^-1 Phi^T M with M the mask: symmetric, idempotent, and it annihilates Phi c for any c).
+ * K = 1 with Phi = 1 is the plain common mode, K = 1 with Phi = the relative gains the gain-weighted one;
+ * K = 3, 6, 10 are the monomials of total degree <= 1, 2, 3 in the focal-plane coordinates.
+ * A unit is SKIPPED -- every sample of it 0 in the output, its K coefficients 0 -- when
+ *     m < K, or
+ *     the Cholesky factorisation G = L L^T meets a pivot p_j = G_jj - sum_{k<j} L_jk^2 <= CM2_CMODE_TAU G_jj
+ *     (it stops at the first such pivot): the surviving detectors do not span the templates.
+ * Every unit has a class: CM2_CMODE_FITTED, CM2_CMODE_EMPTY (m = 0), CM2_CMODE_FEW (0 < m < K), CM2_CMODE_PIVOT.
+ * The class depends on Phi and the flags only.  A non-finite v[k, i] on an unflagged sample makes its own unit's
+ * output non-finite and no other unit's.
+ *
+ * The handle holds Phi (ndet K doubles), the group edges and one class byte per unit.  G is formed from the flags in
+ * registers on every call; nothing of size ns K^2 is stored.
+ *
+ * Order (no floating-point atomics, no sums across threads; the same bits every time): one thread per unit.  G_ab
+ * (a >= b) and b_a start at 0 and take G_ab += Phi_ka Phi_kb, b_a += Phi_ka v[k, i] over the unflagged detectors of
+ * the group in ascending k.  The factor is formed row by row, p_j = G_jj - L_j0^2 - ... - L_j,j-1^2 (left to right),
+ * L_jj = sqrt(p_j), L_ij = (G_ij - L_i0 L_j0 - ... - L_i,j-1 L_j,j-1) / L_jj; then the two triangular solves (row i:
+ * the known terms subtracted in ascending index order, then the division by L_ii), and
+ * out[k, i] = v[k, i] - (((c_0 Phi_k0 + c_1 Phi_k1) + c_2 Phi_k2) + ... + c_{K-1} Phi_k,K-1).  Every product and sum is
+ * rounded on its own.  The result of a unit does not depend on ns, on the other groups or on where the unit lies.
+ *
+ * cm2_cmode_create keeps d_pix (it must not change or be freed while the handle lives) and copies d_modes[ndet K]
+ *   and h_group_edges[ngroups + 1]; classes every unit and counts the classes.  Allocates and synchronises.
+ * cm2_cmode_info: h_info[8] = ns, ndet, ngroups, K, units fitted, empty, few, pivot.
+ * cm2_cmode_apply: d_out = F d_in (nt doubles each).  One launch, no allocation, no synchronisation.  d_out may be
+ *   d_in itself (a thread reads its column before it stores and touches no other); any other overlap is refused.
+ * cm2_cmode_fit: d_coeff[(g K + j) ns + i] = c_j of unit (g, i), 0 for a skipped unit; nothing is subtracted.
+ * cm2_cmode_status: d_status[g ns + i] = the class of unit (g, i), one byte each.  Synchronises.
+ * Refused with CM2_ERR_ARGUMENT, the outputs (and *out) untouched: K outside [1, 10]; ns, ndet or ngroups < 1; edges
+ * that do not ascend strictly from 0 to ndet; NULL pointers; sizes that overflow the index types or the grid
+ * (ndet ns > 2^46, ndet >= 2^31, 2^31 or more workgroups of 256 units); d_out overlapping d_in without being d_in;
+ * d_coeff sharing memory with d_in. */
+#define CM2_CMODE_TAU 0.0009765625          /* 2^-10 */
+#define CM2_CMODE_MAX_K 10
+#define CM2_CMODE_FITTED 0
+#define CM2_CMODE_EMPTY 1
+#define CM2_CMODE_FEW 2
+#define CM2_CMODE_PIVOT 3
+typedef struct cm2_cmode cm2_cmode;
+int cm2_cmode_create(cm2_cmode **out, int64_t ns, int ndet, int ngroups, const int64_t *h_group_edges, int K,
+                     const double *d_modes, const int32_t *d_pix, void *stream);
+int cm2_cmode_destroy(cm2_cmode *h);
+int cm2_cmode_info(const cm2_cmode *h, int64_t *h_info);
+int cm2_cmode_apply(cm2_cmode *h, const double *d_in, double *d_out, void *stream);
+int cm2_cmode_fit(cm2_cmode *h, const double *d_in, double *d_coeff, void *stream);
+int cm2_cmode_status(const cm2_cmode *h, uint8_t *d_status);
+
 /* ---- f3: solution vector <-> full-sky HEALPix maps -------------------------------
  * cm2_cutsky_to_fullsky: d_full is pol arrays of nfull doubles one after the other
  * ([I | Q | U]); component k of observed pixel i, d_map[pol*i + k], goes to
