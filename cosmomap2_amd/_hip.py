@@ -257,3 +257,22 @@ def call(name, *args):
     if rc == ERR_OUT_OF_MEMORY and name in RESTARTABLE and _free_torch_cache():
         rc = fn(*args)
     check(rc)
+
+
+class Handle(object):
+    """Owner of one library object: ``.h`` the handle (None when there is none), ``.keep`` whatever the C side
+    borrows and must outlive it, ``destroy`` the name of the entry point that frees it.  A subclass sets ``.h``
+    through ``Handle.__init__`` once its create call has succeeded; ``__del__`` tolerates an object whose
+    constructor raised before that, and an interpreter that is shutting down."""
+    h = keep = None
+
+    def __init__(self, destroy, handle, keep=None):
+        self._destroy, self.h, self.keep = destroy, handle, keep
+
+    def __del__(self):
+        h, self.h = self.h, None
+        if h:
+            try:
+                getattr(load(), self._destroy)(h)
+            except Exception:
+                pass

@@ -12,13 +12,8 @@
 // its own; no floating-point atomic, no cross-lane sum):
 //   1. G_ab (a >= b) and b_a start at 0; the unflagged detectors of the group in ascending k:
 //      G_ab += Phi_ka Phi_kb,  b_a += Phi_ka v[k, i].
-//   2. Factor, skip test and the two solves as written at the top of cm2_hwpss.hip: row by row,
-//      p_j = G_jj - L_j0^2 - ... - L_j,j-1^2 (left to right), the unit is skipped at the first p_j <= CM2_CMODE_TAU G_jj
-//      (or when m < K), L_jj = sqrt(p_j), L_ij = (G_ij - L_i0 L_j0 - ... - L_i,j-1 L_j,j-1) / L_jj;
-//      y_i = (b_i - L_i0 y_0 - ... - L_i,i-1 y_i-1) / L_ii for i = 0..K-1, then
-//      c_i = (y_i - L_i+1,i c_i+1 - ... - L_K-1,i c_K-1) / L_ii for i = K-1..0, the terms subtracted left to right.
-//      (A lane goes on after a failed pivot, the others of its wave need the instructions anyway; what it computes
-//      from there on is never used.)
+//   2. Factor, skip test and the two solves of cm2_fit.h, which has the order of their operations; the unit is
+//      skipped when a pivot fails with tau = CM2_CMODE_TAU (or when m < K).
 //   3. p = c_0 Phi_k0, then p += c_j Phi_kj for j = 1..K-1; out[k, i] = v[k, i] - p on an unflagged sample, 0 on a
 //      flagged one and on every sample of a skipped unit.
 // A thread reads its whole column for step 1 before its first store and touches no other column: out may be v itself.
@@ -59,6 +54,9 @@ __device__ __forceinline__ Unit my_unit(const Shape &s)
 // samples there are few threads, so the memory parallelism has to come from inside the walk
 template <int K>
 constexpr int kAhead = K <= 6 ? 8 : 4;
+
+template <int K>
+using KConst = std::integral_constant<int, K>;
 
 // step 1.  WITH_B = false: G and m only (the class of a unit depends on Phi and the flags alone)
 template <int K, bool WITH_B>
@@ -104,51 +102,6 @@ __device__ __forceinline__ int gram(const Shape &s, const Unit &u, const double 
     return m;
 }
 
-// step 2, the factor: G becomes L; true when a pivot failed the test
-template <int K>
-__device__ __forceinline__ bool factor(double (&G)[cp::packed(K)], double tau)
-{
-    bool failed = false;
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-        const double gjj = G[cp::packed_at(j, j)];
-        double pv = gjj;
-#pragma unroll
-        for (int k = 0; k < j; ++k) pv -= G[cp::packed_at(j, k)] * G[cp::packed_at(j, k)];
-        failed = failed || !(pv > tau * gjj);
-        const double ljj = sqrt(pv);
-        G[cp::packed_at(j, j)] = ljj;
-#pragma unroll
-        for (int i = j + 1; i < K; ++i) {
-            double t = G[cp::packed_at(i, j)];
-#pragma unroll
-            for (int k = 0; k < j; ++k) t -= G[cp::packed_at(i, k)] * G[cp::packed_at(j, k)];
-            G[cp::packed_at(i, j)] = t / ljj;
-        }
-    }
-    return failed;
-}
-
-// step 2, the two solves: b becomes c
-template <int K>
-__device__ __forceinline__ void solve(const double (&L)[cp::packed(K)], double (&y)[K])
-{
-#pragma unroll
-    for (int i = 0; i < K; ++i) {
-        double a = y[i];
-#pragma unroll
-        for (int k = 0; k < i; ++k) a -= L[cp::packed_at(i, k)] * y[k];
-        y[i] = a / L[cp::packed_at(i, i)];
-    }
-#pragma unroll
-    for (int i = K - 1; i >= 0; --i) {
-        double a = y[i];
-#pragma unroll
-        for (int k = i + 1; k < K; ++k) a -= L[cp::packed_at(k, i)] * y[k];
-        y[i] = a / L[cp::packed_at(i, i)];
-    }
-}
-
 __device__ __forceinline__ int class_of(int m, int K, bool failed)
 {
     return m == 0 ? cp::kEmpty : m < K ? cp::kFew : failed ? cp::kPivot : cp::kFitted;
@@ -161,9 +114,8 @@ __device__ __forceinline__ int fit_unit(const Shape &s, const Unit &u, const dou
     double G[cp::packed(K)];
     const int m = gram<K, true>(s, u, v, G, c);
     if (m < K) return class_of(m, K, false);
-    const bool failed = factor<K>(G, tau);
-    if (failed) return cp::kPivot;
-    solve<K>(G, c);
+    if (fit::factor(KConst<K>{}, G, tau)) return cp::kPivot;
+    fit::solve(KConst<K>{}, G, c);
     return cp::kFitted;
 }
 
@@ -235,7 +187,7 @@ __global__ __launch_bounds__(cp::kThreads) void k_cmode_class(Shape s, double ta
     if (u.i < s.ns) {
         double G[cp::packed(K)], unused[K];
         const int m = gram<K, false>(s, u, nullptr, G, unused);
-        const bool failed = m >= K ? factor<K>(G, tau) : false;
+        const bool failed = m >= K ? fit::factor(KConst<K>{}, G, tau) : false;
         const int cls = class_of(m, K, failed);
         status[u.g * s.ns + u.i] = (uint8_t)cls;
         atomicAdd(&tally[cls], 1u);
@@ -268,54 +220,11 @@ extern "C" int cm2_cmode_destroy(cm2_cmode *h)
 
 namespace {
 
-template <template <int> class Launch, typename... A>
-void by_K(int K, A... a)
-{
-    switch (K) {
-        case 1: Launch<1>::go(a...); break;
-        case 2: Launch<2>::go(a...); break;
-        case 3: Launch<3>::go(a...); break;
-        case 4: Launch<4>::go(a...); break;
-        case 5: Launch<5>::go(a...); break;
-        case 6: Launch<6>::go(a...); break;
-        case 7: Launch<7>::go(a...); break;
-        case 8: Launch<8>::go(a...); break;
-        case 9: Launch<9>::go(a...); break;
-        default: Launch<10>::go(a...); break;
-    }
-}
-
-template <int K>
-struct ApplyLaunch {
-    static void go(const cm2_cmode *h, const double *d_in, double *d_out, hipStream_t st)
-    {
-        k_cmode_apply<K><<<dim3((unsigned)h->launch.blocks), cp::kThreads, 0, st>>>(h->shape(), CM2_CMODE_TAU, d_in,
-                                                                                    d_out);
-    }
-};
-template <int K>
-struct FitLaunch {
-    static void go(const cm2_cmode *h, const double *d_in, double *d_coeff, hipStream_t st)
-    {
-        k_cmode_fit<K><<<dim3((unsigned)h->launch.blocks), cp::kThreads, 0, st>>>(h->shape(), CM2_CMODE_TAU, d_in,
-                                                                                  d_coeff);
-    }
-};
-template <int K>
-struct ClassLaunch {
-    static void go(const cm2_cmode *h, unsigned long long *d_counts, hipStream_t st)
-    {
-        k_cmode_class<K><<<dim3((unsigned)h->launch.blocks), cp::kThreads, 0, st>>>(h->shape(), CM2_CMODE_TAU,
-                                                                                    h->d_status, d_counts);
-    }
-};
-
 int cmode_fill(cm2_cmode *h, const int64_t *h_edges, const double *d_modes, hipStream_t st)
 {
     std::vector<int32_t> e((size_t)h->ngroups + 1);
     for (size_t g = 0; g < e.size(); ++g) e[g] = (int32_t)h_edges[g];
-    CM2_HIP(cm2::dev_malloc(&h->d_gedges, sizeof(int32_t) * e.size()));
-    CM2_HIP(cm2::upload(h->d_gedges, e.data(), sizeof(int32_t) * e.size(), st));
+    if (int rc = dev_put(&h->d_gedges, e.data(), e.size(), st)) return rc;
     const size_t mbytes = sizeof(double) * (size_t)h->ndet * (size_t)h->K;
     CM2_HIP(cm2::dev_malloc(&h->d_modes, mbytes));
     CM2_HIP(hipMemcpyAsync(h->d_modes, d_modes, mbytes, hipMemcpyDeviceToDevice, st));
@@ -323,20 +232,16 @@ int cmode_fill(cm2_cmode *h, const int64_t *h_edges, const double *d_modes, hipS
     DevTemp<unsigned long long> counts;
     CM2_HIP(counts.alloc(4));
     CM2_HIP(hipMemsetAsync(counts.p, 0, 4 * sizeof(unsigned long long), st));
-    by_K<ClassLaunch>(h->K, (const cm2_cmode *)h, counts.p, st);
+    dispatch_int<1, cp::kMaxK>(h->K, [&](auto K) {
+        k_cmode_class<K><<<dim3((unsigned)h->launch.blocks), cp::kThreads, 0, st>>>(h->shape(), CM2_CMODE_TAU,
+                                                                                    h->d_status, counts.p);
+    });
     CM2_LAUNCH_OK();
     unsigned long long got[4];
     CM2_HIP(cm2::download(got, counts.p, sizeof(got), st));
     CM2_HIP(hipStreamSynchronize(st));
     for (int c = 0; c < 4; ++c) h->nclass[c] = (int64_t)got[c];
     return 0;
-}
-
-// do a[0, na) and b[0, nb) share a byte?
-bool overlap(const double *a, int64_t na, const double *b, int64_t nb)
-{
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-    return x < y + (uintptr_t)nb * sizeof(double) && y < x + (uintptr_t)na * sizeof(double);
 }
 
 }  // namespace
@@ -387,9 +292,12 @@ extern "C" int cm2_cmode_apply(cm2_cmode *h, const double *d_in, double *d_out, 
 {
     CM2_CHECK(h, "cm2_cmode_apply: null handle");
     CM2_CHECK(d_in && d_out, "cm2_cmode_apply: null vector");
-    CM2_CHECK(d_in == d_out || !overlap(d_in, h->launch.nt, d_out, h->launch.nt),
+    CM2_CHECK(d_in == d_out || !ranges_overlap(d_in, h->launch.nt, d_out, h->launch.nt),
               "cm2_cmode_apply: the output must be the input itself or not overlap it");
-    by_K<ApplyLaunch>(h->K, (const cm2_cmode *)h, d_in, d_out, as_stream(stream));
+    dispatch_int<1, cp::kMaxK>(h->K, [&](auto K) {
+        k_cmode_apply<K><<<dim3((unsigned)h->launch.blocks), cp::kThreads, 0, as_stream(stream)>>>(
+            h->shape(), CM2_CMODE_TAU, d_in, d_out);
+    });
     CM2_LAUNCH_OK();
     return 0;
 }
@@ -398,9 +306,12 @@ extern "C" int cm2_cmode_fit(cm2_cmode *h, const double *d_in, double *d_coeff, 
 {
     CM2_CHECK(h, "cm2_cmode_fit: null handle");
     CM2_CHECK(d_in && d_coeff, "cm2_cmode_fit: null vector");
-    CM2_CHECK(!overlap(d_in, h->launch.nt, d_coeff, h->launch.units * h->K),
+    CM2_CHECK(!ranges_overlap(d_in, h->launch.nt, d_coeff, h->launch.units * h->K),
               "cm2_cmode_fit: the coefficients must not alias the input");
-    by_K<FitLaunch>(h->K, (const cm2_cmode *)h, d_in, d_coeff, as_stream(stream));
+    dispatch_int<1, cp::kMaxK>(h->K, [&](auto K) {
+        k_cmode_fit<K><<<dim3((unsigned)h->launch.blocks), cp::kThreads, 0, as_stream(stream)>>>(
+            h->shape(), CM2_CMODE_TAU, d_in, d_coeff);
+    });
     CM2_LAUNCH_OK();
     return 0;
 }

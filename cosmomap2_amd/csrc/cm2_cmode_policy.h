@@ -10,6 +10,8 @@
 #pragma once
 #include <cstdint>
 
+#include "cm2_fit.h"
+
 namespace cm2 {
 namespace cmode {
 
@@ -22,8 +24,8 @@ enum Class { kFitted = 0, kEmpty = 1, kFew = 2, kPivot = 3 };
 enum Status { kOk = 0, kBadK = 1, kBadSize = 2, kBadEdges = 3, kTooLarge = 4 };
 
 // (constexpr: callable from device code as well)
-constexpr int packed(int K) { return K * (K + 1) / 2; }                   // doubles of the lower triangle
-constexpr int packed_at(int i, int j) { return i * (i + 1) / 2 + j; }     // entry (i, j), j <= i
+using fit::packed;          // doubles of the lower triangle
+using fit::packed_at;       // entry (i, j), j <= i
 constexpr int64_t blocks_per_group(int64_t ns) { return (ns + kThreads - 1) / kThreads; }
 
 struct Launch {
@@ -36,10 +38,7 @@ inline Status check(Launch *l, int64_t ns, int64_t ndet, int64_t ngroups, const 
 {
     if (K < 1 || K > kMaxK) return kBadK;
     if (ns < 1 || ndet < 1 || ngroups < 1 || !edges) return kBadSize;
-    if (ngroups > ndet) return kBadEdges;
-    if (edges[0] != 0 || edges[ngroups] != ndet) return kBadEdges;
-    for (int64_t g = 0; g < ngroups; ++g)
-        if (edges[g + 1] <= edges[g]) return kBadEdges;
+    if (!fit::edges_ok(edges, ngroups, ndet)) return kBadEdges;
     const int64_t lim = (int64_t)1 << 31;
     if (ndet >= lim) return kTooLarge;
     if (ndet > (((int64_t)1 << 46) / ns)) return kTooLarge;

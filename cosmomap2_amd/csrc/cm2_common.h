@@ -6,6 +6,7 @@
 #include <cstring>
 #include <mutex>
 #include <string>
+#include <type_traits>
 
 #include "../../include/cosmomap2.h"
 
@@ -73,6 +74,26 @@ static inline int grid_for(int64_t n, int block = kBlock, int max_blocks = kNumC
 
 static inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
+// f(std::integral_constant<int, N>{}) for the N in [Lo, Hi] that equals n; any other n takes Hi.  With a generic
+// lambda, `[&](auto N) { kernel<N><<<...>>>(...); }` picks the instantiation of a run-time value.
+template <int Lo, int Hi, class F>
+inline auto dispatch_int(int n, F &&f)
+{
+    if constexpr (Lo < Hi) {
+        if (n == Lo) return f(std::integral_constant<int, Lo>{});
+        return dispatch_int<Lo + 1, Hi>(n, f);
+    } else {
+        return f(std::integral_constant<int, Hi>{});
+    }
+}
+
+// do a[0, na) and b[0, nb) share a byte?
+inline bool ranges_overlap(const double *a, int64_t na, const double *b, int64_t nb)
+{
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return x < y + (uintptr_t)nb * sizeof(double) && y < x + (uintptr_t)na * sizeof(double);
+}
+
 // hipFuncAttributeMaxDynamicSharedMemorySize is a per-device property of a kernel: granted[] (one
 // static array per kernel instance at the call site) remembers what each device was given, so the
 // runtime is asked once per device and again only when a launch needs more.
@@ -100,6 +121,15 @@ struct NoCopy {
     NoCopy(const NoCopy &) = delete;
     NoCopy &operator=(const NoCopy &) = delete;
 };
+
+// a new device array *dst holding the count entries of the host array src (one entry is allocated for count = 0)
+template <typename T>
+inline int dev_put(T **dst, const T *src, size_t count, hipStream_t st)
+{
+    CM2_HIP(dev_malloc(dst, sizeof(T) * (count ? count : 1)));
+    if (count) CM2_HIP(upload(*dst, src, sizeof(T) * count, st));
+    return 0;
+}
 
 // Scratch allocation of a setup routine: freed on every exit path (the CM2_HIP / CM2_CHECK
 // macros return early on failure).  keep() hands the buffer over to a longer-lived owner.

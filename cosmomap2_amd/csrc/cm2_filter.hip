@@ -505,13 +505,7 @@ extern "C" void cm2_filter_destroy(cm2_filter *f)
 
 namespace {
 
-template <typename T>
-int upload(T **dst, const T *src, size_t count, hipStream_t st)
-{
-    CM2_HIP(cm2::dev_malloc(dst, sizeof(T) * (count ? count : 1)));
-    if (count) CM2_HIP(cm2::upload(*dst, src, sizeof(T) * count, st));
-    return 0;
-}
+constexpr int kMinPolyK = 2, kMaxPolyK = 8;      // K = order + 1 of the Legendre filter
 
 template <int K>
 int setup_poly(cm2_filter *f, hipStream_t st)
@@ -573,23 +567,13 @@ int filter_fill(cm2_filter *f, int64_t nt, int64_t nseg, const int64_t *h_start,
     f->d_pix = d_pix;
     f->h_start.assign(h_start, h_start + nseg);
     f->h_len.assign(h_len, h_len + nseg);
-    if (int rc = upload(&f->d_start, h_start, (size_t)nseg, st)) return rc;
-    if (int rc = upload(&f->d_len, h_len, (size_t)nseg, st)) return rc;
-    if (int rc = upload(&f->d_prev_end, prev_end.data(), (size_t)nseg, st)) return rc;
+    if (int rc = dev_put(&f->d_start, h_start, (size_t)nseg, st)) return rc;
+    if (int rc = dev_put(&f->d_len, h_len, (size_t)nseg, st)) return rc;
+    if (int rc = dev_put(&f->d_prev_end, prev_end.data(), (size_t)nseg, st)) return rc;
     if (order > 0) {
-        if (int rc = upload(&f->d_toff, h_table_off, (size_t)nseg, st)) return rc;
-        if (int rc = upload(&f->d_table, h_table, (size_t)table_len, st)) return rc;
-        int rc = 0;
-        switch (K) {
-            case 2: rc = setup_poly<2>(f, st); break;
-            case 3: rc = setup_poly<3>(f, st); break;
-            case 4: rc = setup_poly<4>(f, st); break;
-            case 5: rc = setup_poly<5>(f, st); break;
-            case 6: rc = setup_poly<6>(f, st); break;
-            case 7: rc = setup_poly<7>(f, st); break;
-            default: rc = setup_poly<8>(f, st); break;
-        }
-        if (rc) return rc;
+        if (int rc = dev_put(&f->d_toff, h_table_off, (size_t)nseg, st)) return rc;
+        if (int rc = dev_put(&f->d_table, h_table, (size_t)table_len, st)) return rc;
+        if (int rc = dispatch_int<kMinPolyK, kMaxPolyK>(K, [&](auto Kc) { return setup_poly<Kc>(f, st); })) return rc;
         std::vector<uint8_t> h_kind((size_t)nseg);
         if (nseg)
             CM2_HIP(cm2::download(h_kind.data(), f->d_kind, (size_t)nseg, st));
@@ -650,15 +634,7 @@ extern "C" int cm2_filter_apply(const cm2_filter *f, const double *d_in, double 
                                                               f->d_prev_end, f->nt, f->d_pix, d_in,
                                                               d_out);
     } else {
-        switch (f->order + 1) {
-            case 2: launch_poly<2>(f, d_in, d_out, st); break;
-            case 3: launch_poly<3>(f, d_in, d_out, st); break;
-            case 4: launch_poly<4>(f, d_in, d_out, st); break;
-            case 5: launch_poly<5>(f, d_in, d_out, st); break;
-            case 6: launch_poly<6>(f, d_in, d_out, st); break;
-            case 7: launch_poly<7>(f, d_in, d_out, st); break;
-            default: launch_poly<8>(f, d_in, d_out, st); break;
-        }
+        dispatch_int<kMinPolyK, kMaxPolyK>(f->order + 1, [&](auto K) { launch_poly<K>(f, d_in, d_out, st); });
     }
     CM2_LAUNCH_OK();
     return 0;
@@ -710,8 +686,7 @@ int filter_windows_build(cm2_filter *f, const uint32_t *d_idx, uint64_t plan_id,
         return 0;
     }
     CM2_CHECK(f->nseg < ((int64_t)1 << 31) && f->nwin < ((int64_t)1 << 31), "too many chunks");
-    CM2_HIP(cm2::dev_malloc(&f->d_wins, sizeof(FilterWin) * wins.size()));
-    CM2_HIP(cm2::upload(f->d_wins, wins.data(), sizeof(FilterWin) * wins.size(), st));
+    if (int rc = dev_put(&f->d_wins, wins.data(), wins.size(), st)) return rc;
     auto keys = [&](uint64_t *k, uint16_t *v) {
         k_win_keys<<<grid_for(f->nwin * kPermWin), kBlock, 0, st>>>(f->d_wins, f->nwin, d_idx, k, v);
     };
@@ -756,16 +731,9 @@ extern "C" int cm2_filter_apply_tiles(cm2_filter *f, const cm2_tiles *tiles, con
     if (f->win_memset && nvalid) CM2_HIP(hipMemsetAsync(d_out_tb, 0, sizeof(double) * nvalid, st));
     *h_done = 1;
     if (f->nwin == 0) return 0;
-    switch (f->order == 0 ? 0 : f->order + 1) {
-        case 0: return launch_windows<0>(f, d_in_tb, d_out_tb, st);
-        case 2: return launch_windows<2>(f, d_in_tb, d_out_tb, st);
-        case 3: return launch_windows<3>(f, d_in_tb, d_out_tb, st);
-        case 4: return launch_windows<4>(f, d_in_tb, d_out_tb, st);
-        case 5: return launch_windows<5>(f, d_in_tb, d_out_tb, st);
-        case 6: return launch_windows<6>(f, d_in_tb, d_out_tb, st);
-        case 7: return launch_windows<7>(f, d_in_tb, d_out_tb, st);
-        default: return launch_windows<8>(f, d_in_tb, d_out_tb, st);
-    }
+    if (f->order == 0) return launch_windows<0>(f, d_in_tb, d_out_tb, st);
+    return dispatch_int<kMinPolyK, kMaxPolyK>(f->order + 1,
+                                              [&](auto K) { return launch_windows<K>(f, d_in_tb, d_out_tb, st); });
 }
 
 extern "C" int cm2_ground_subtract(int64_t nt, const int32_t *d_bin, const double *d_binned,

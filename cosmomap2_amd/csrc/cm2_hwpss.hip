@@ -14,11 +14,8 @@
 //   4. a unit's sum is 0 + its segments' sums in ascending segment order (k_hwpss_solve, k_hwpss_factor).
 // There is no floating-point atomic: two applications give the same bits.
 //
-// Factor (k_hwpss_factor, once): G = L L^T, row by row, p_j = G_jj - L_j0^2 - ... - L_j,j-1^2 (left to right),
-// the unit is skipped at the first p_j <= CM2_HWPSS_TAU G_jj (or when G_00 = m < K); L_jj = sqrt(p_j),
-// L_ij = (G_ij - L_i0 L_j0 - ... - L_i,j-1 L_j,j-1) / L_jj.
-// Solve (k_hwpss_solve): y_i = (b_i - L_i0 y_0 - ... - L_i,i-1 y_i-1) / L_ii for i = 0..K-1, then
-// c_i = (y_i - L_i+1,i c_i+1 - ... - L_K-1,i c_K-1) / L_ii for i = K-1..0, the terms subtracted left to right.
+// Factor (k_hwpss_factor, once) and solve (k_hwpss_solve): cm2_fit.h has them and the order of their operations;
+// the unit is skipped when a pivot fails with tau = CM2_HWPSS_TAU (or when G_00 = m < K).
 // Subtract (k_hwpss_subtract): p = c_0, then p += c_{2n-1} T_{2n-1}, p += c_{2n} T_{2n} for n = 1..H; out = v - p on
 // an unflagged sample, 0 on a flagged one and on every sample of a skipped unit.
 #include "cm2_common.h"
@@ -147,22 +144,8 @@ __global__ __launch_bounds__(64) void k_hwpss_factor(PlanDev p, int K, double ta
     if (threadIdx.x != 0) return;
     double *L = factor + unit * hp::packed(K);
     int mark = G[0] < (double)K ? 1 : 0;               // G_00 = the number of unflagged samples, exact
-    for (int j = 0; j < K && mark == 0; ++j) {
-        const double gjj = G[j * K + j];
-        double pv = gjj;
-        for (int k = 0; k < j; ++k) pv -= G[j * K + k] * G[j * K + k];
-        if (!(pv > tau * gjj)) {
-            mark = 2;
-            break;
-        }
-        const double ljj = sqrt(pv);
-        G[j * K + j] = ljj;
-        for (int i = j + 1; i < K; ++i) {
-            double v = G[i * K + j];
-            for (int k = 0; k < j; ++k) v -= G[i * K + k] * G[j * K + k];
-            G[i * K + j] = v / ljj;
-        }
-    }
+    const fit::RowMajor rows{G, K};
+    if (mark == 0 && fit::factor(K, rows, tau)) mark = 2;
     for (int i = 0; i < K; ++i)
         for (int j = 0; j <= i; ++j) L[hp::packed_at(i, j)] = mark ? 0.0 : G[i * K + j];
     skip[unit] = (uint8_t)mark;
@@ -225,16 +208,7 @@ __global__ __launch_bounds__(64) void k_hwpss_solve(PlanDev p, int K, const uint
     }
     __syncthreads();
     if (j != 0) return;
-    for (int i = 0; i < K; ++i) {
-        double a = y[i];
-        for (int k = 0; k < i; ++k) a -= L[hp::packed_at(i, k)] * y[k];
-        y[i] = a / L[hp::packed_at(i, i)];
-    }
-    for (int i = K - 1; i >= 0; --i) {
-        double a = y[i];
-        for (int k = i + 1; k < K; ++k) a -= L[hp::packed_at(k, i)] * y[k];
-        y[i] = a / L[hp::packed_at(i, i)];
-    }
+    fit::solve(K, L, y);
     for (int i = 0; i < K; ++i) coeff[unit * K + i] = y[i];
 }
 
@@ -304,61 +278,13 @@ extern "C" int cm2_hwpss_destroy(cm2_hwpss *h)
 
 namespace {
 
-template <typename T>
-int put(T **dst, const std::vector<T> &src, hipStream_t st)
-{
-    CM2_HIP(cm2::dev_malloc(dst, sizeof(T) * src.size()));
-    CM2_HIP(cm2::upload(*dst, src.data(), sizeof(T) * src.size(), st));
-    return 0;
-}
-
-template <template <int> class Launch, typename... A>
-void by_harm(int nharm, A... a)
-{
-    switch (nharm) {
-        case 1: Launch<1>::go(a...); break;
-        case 2: Launch<2>::go(a...); break;
-        case 3: Launch<3>::go(a...); break;
-        case 4: Launch<4>::go(a...); break;
-        case 5: Launch<5>::go(a...); break;
-        case 6: Launch<6>::go(a...); break;
-        case 7: Launch<7>::go(a...); break;
-        default: Launch<8>::go(a...); break;
-    }
-}
-
-template <int H>
-struct GramLaunch {
-    static void go(const cm2_hwpss *h, double *gp, hipStream_t st)
-    {
-        const dim3 grid((unsigned)h->plan.nsegs, (unsigned)h->plan.K);
-        k_hwpss_gram<H><<<grid, hp::kThreads, 0, st>>>(h->dev(), h->d_pix, h->d_cos, h->d_sin, gp);
-    }
-};
-template <int H>
-struct SumsLaunch {
-    static void go(const cm2_hwpss *h, const double *d_in, hipStream_t st)
-    {
-        k_hwpss_sums<H><<<dim3((unsigned)h->plan.nsegs), hp::kThreads, 0, st>>>(h->dev(), h->d_skip, h->d_pix, d_in,
-                                                                                 h->d_cos, h->d_sin, h->d_partial);
-    }
-};
-template <int H>
-struct SubtractLaunch {
-    static void go(const cm2_hwpss *h, const double *d_in, double *d_out, hipStream_t st)
-    {
-        k_hwpss_subtract<H><<<dim3((unsigned)h->plan.nsegs), hp::kThreads, 0, st>>>(
-            h->dev(), h->d_skip, h->d_coeff, h->d_pix, d_in, h->d_cos, h->d_sin, d_out);
-    }
-};
-
 int hwpss_fill(cm2_hwpss *h, const double *d_chi, hipStream_t st)
 {
     const hp::Plan &p = h->plan;
     const int K = p.K;
-    if (int rc = put(&h->d_edges, p.edges, st)) return rc;
-    if (int rc = put(&h->d_seg_first, p.seg_first, st)) return rc;
-    if (int rc = put(&h->d_seg_chunk, p.seg_chunk, st)) return rc;
+    if (int rc = dev_put(&h->d_edges, p.edges.data(), p.edges.size(), st)) return rc;
+    if (int rc = dev_put(&h->d_seg_first, p.seg_first.data(), p.seg_first.size(), st)) return rc;
+    if (int rc = dev_put(&h->d_seg_chunk, p.seg_chunk.data(), p.seg_chunk.size(), st)) return rc;
     CM2_HIP(cm2::dev_malloc(&h->d_cos, sizeof(double) * (size_t)p.ns));
     CM2_HIP(cm2::dev_malloc(&h->d_sin, sizeof(double) * (size_t)p.ns));
     CM2_HIP(cm2::dev_malloc(&h->d_factor, sizeof(double) * (size_t)(p.nunits * hp::packed(K))));
@@ -369,7 +295,10 @@ int hwpss_fill(cm2_hwpss *h, const double *d_chi, hipStream_t st)
     CM2_LAUNCH_OK();
     DevTemp<double> gp;                                // the Gram sums of every segment: create time only
     CM2_HIP(gp.alloc((size_t)(p.nsegs * K * K)));
-    by_harm<GramLaunch>(p.nharm, (const cm2_hwpss *)h, gp.p, st);
+    dispatch_int<1, hp::kMaxHarm>(h->plan.nharm, [&](auto H) {
+        const dim3 grid((unsigned)p.nsegs, (unsigned)K);
+        k_hwpss_gram<H><<<grid, hp::kThreads, 0, st>>>(h->dev(), h->d_pix, h->d_cos, h->d_sin, gp.p);
+    });
     CM2_LAUNCH_OK();
     k_hwpss_factor<<<dim3((unsigned)p.nunits), 64, 0, st>>>(h->dev(), K, CM2_HWPSS_TAU, gp, h->d_factor, h->d_skip);
     CM2_LAUNCH_OK();
@@ -378,13 +307,6 @@ int hwpss_fill(cm2_hwpss *h, const double *d_chi, hipStream_t st)
     CM2_HIP(hipStreamSynchronize(st));
     for (uint8_t m : marks) h->nmark[m < 3 ? m : 0]++;
     return 0;
-}
-
-// do a[0, na) and b[0, nb) share a byte?
-bool overlap(const double *a, int64_t na, const double *b, int64_t nb)
-{
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-    return x < y + (uintptr_t)nb * sizeof(double) && y < x + (uintptr_t)na * sizeof(double);
 }
 
 }  // namespace
@@ -436,7 +358,10 @@ namespace {
 
 int hwpss_fit_into(cm2_hwpss *h, const double *d_in, double *d_coeff, hipStream_t st)
 {
-    by_harm<SumsLaunch>(h->plan.nharm, (const cm2_hwpss *)h, d_in, st);
+    dispatch_int<1, hp::kMaxHarm>(h->plan.nharm, [&](auto H) {
+        k_hwpss_sums<H><<<dim3((unsigned)h->plan.nsegs), hp::kThreads, 0, st>>>(h->dev(), h->d_skip, h->d_pix, d_in,
+                                                                                 h->d_cos, h->d_sin, h->d_partial);
+    });
     CM2_LAUNCH_OK();
     k_hwpss_solve<<<dim3((unsigned)h->plan.nunits), 64, 0, st>>>(h->dev(), h->plan.K, h->d_skip, h->d_factor,
                                                                   h->d_partial, d_coeff);
@@ -450,7 +375,7 @@ extern "C" int cm2_hwpss_fit(cm2_hwpss *h, const double *d_in, double *d_coeff, 
 {
     CM2_CHECK(h, "cm2_hwpss_fit: null handle");
     CM2_CHECK(d_in && d_coeff, "cm2_hwpss_fit: null vector");
-    CM2_CHECK(!overlap(d_in, h->plan.nt, d_coeff, h->plan.nunits * h->plan.K),
+    CM2_CHECK(!ranges_overlap(d_in, h->plan.nt, d_coeff, h->plan.nunits * h->plan.K),
               "cm2_hwpss_fit: the coefficients must not alias the input");
     return hwpss_fit_into(h, d_in, d_coeff, as_stream(stream));
 }
@@ -459,10 +384,13 @@ extern "C" int cm2_hwpss_apply(cm2_hwpss *h, const double *d_in, double *d_out, 
 {
     CM2_CHECK(h, "cm2_hwpss_apply: null handle");
     CM2_CHECK(d_in && d_out, "cm2_hwpss_apply: null vector");
-    CM2_CHECK(!overlap(d_in, h->plan.nt, d_out, h->plan.nt), "cm2_hwpss_apply: output must not alias the input");
+    CM2_CHECK(!ranges_overlap(d_in, h->plan.nt, d_out, h->plan.nt), "cm2_hwpss_apply: output must not alias the input");
     hipStream_t st = as_stream(stream);
     if (int rc = hwpss_fit_into(h, d_in, h->d_coeff, st)) return rc;
-    by_harm<SubtractLaunch>(h->plan.nharm, (const cm2_hwpss *)h, d_in, d_out, st);
+    dispatch_int<1, hp::kMaxHarm>(h->plan.nharm, [&](auto H) {
+        k_hwpss_subtract<H><<<dim3((unsigned)h->plan.nsegs), hp::kThreads, 0, st>>>(
+            h->dev(), h->d_skip, h->d_coeff, h->d_pix, d_in, h->d_cos, h->d_sin, d_out);
+    });
     CM2_LAUNCH_OK();
     return 0;
 }
@@ -471,7 +399,7 @@ extern "C" int cm2_hwpss_tables(const cm2_hwpss *h, double *d_cos, double *d_sin
 {
     CM2_CHECK(h, "cm2_hwpss_tables: null handle");
     CM2_CHECK(d_cos && d_sin, "cm2_hwpss_tables: null array");
-    CM2_CHECK(!overlap(d_cos, h->plan.ns, d_sin, h->plan.ns), "cm2_hwpss_tables: the two outputs overlap");
+    CM2_CHECK(!ranges_overlap(d_cos, h->plan.ns, d_sin, h->plan.ns), "cm2_hwpss_tables: the two outputs overlap");
     hipStream_t st = as_stream(stream);
     const size_t bytes = sizeof(double) * (size_t)h->plan.ns;
     CM2_HIP(hipMemcpyAsync(d_cos, h->d_cos, bytes, hipMemcpyDeviceToDevice, st));

@@ -14,6 +14,8 @@
 #include <cstdint>
 #include <vector>
 
+#include "cm2_fit.h"
+
 namespace cm2 {
 namespace hwpss {
 
@@ -26,8 +28,8 @@ constexpr int kMaxK = 2 * kMaxHarm + 1;
 // (constexpr: callable from device code as well)
 constexpr int templates(int nharm) { return 2 * nharm + 1; }
 constexpr int64_t segments_in(int64_t n) { return (n + kSeg - 1) / kSeg; }
-constexpr int packed(int K) { return K * (K + 1) / 2; }       // doubles of a lower-triangular factor
-constexpr int packed_at(int i, int j) { return i * (i + 1) / 2 + j; }     // L_ij, j <= i
+using fit::packed;          // doubles of a lower-triangular factor
+using fit::packed_at;       // L_ij, j <= i
 
 enum Status { kOk = 0, kBadHarm = 1, kBadSize = 2, kBadEdges = 3, kTooLarge = 4 };
 
@@ -45,10 +47,7 @@ inline Status make_plan(Plan *p, int64_t ns, int64_t ndet, int64_t nchunks, cons
 {
     if (nharm < 1 || nharm > kMaxHarm) return kBadHarm;
     if (ns < 1 || ndet < 1 || nchunks < 1 || !edges) return kBadSize;
-    if (nchunks > ns) return kBadEdges;
-    if (edges[0] != 0 || edges[nchunks] != ns) return kBadEdges;
-    for (int64_t c = 0; c < nchunks; ++c)
-        if (edges[c + 1] <= edges[c]) return kBadEdges;
+    if (!fit::edges_ok(edges, nchunks, ns)) return kBadEdges;
     const int64_t lim = (int64_t)1 << 31;
     if (ns >= ((int64_t)1 << 40) || ndet >= lim || nchunks >= lim) return kTooLarge;
     if (ndet > (((int64_t)1 << 46) / ns)) return kTooLarge;

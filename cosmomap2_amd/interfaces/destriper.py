@@ -84,17 +84,16 @@ def _check_offsets_args(P, blocksize, baseline_length, weights):
     return sizes, Lb, w, per_block
 
 
-class _Offsets(object):
+class _Offsets(_hip.Handle):
     """Owns a cm2_offsets handle and the device pixel stream it reads."""
 
     def __init__(self, d_pix, sizes, Lb, w):
-        self.h = None
         self.pix = d_pix
         sz = np.ascontiguousarray(sizes, dtype=np.int64)
         h = ctypes.c_void_p()
         _hip.call("cm2_offsets_create", ctypes.byref(h), D.ptr(d_pix), int(sz.sum()), sz.ctypes.data_as(_I64P),
                   len(sizes), int(Lb), None if w is None else w.ctypes.data_as(_DBLP), D.stream())
-        self.h = h
+        _hip.Handle.__init__(self, "cm2_offsets_destroy", h)
 
     def info(self):
         info = (ctypes.c_int64 * 8)()
@@ -106,14 +105,6 @@ class _Offsets(object):
         nvalid, wsum = np.empty(na, dtype=np.int64), np.empty(na, dtype=np.float64)
         _hip.call("cm2_offsets_counts", self.h, nvalid.ctypes.data, wsum.ctypes.data, D.stream())
         return nvalid, wsum
-
-    def __del__(self):
-        if getattr(self, "h", None):
-            try:
-                _hip.load().cm2_offsets_destroy(self.h)
-            except Exception:
-                pass
-            self.h = None
 
 
 class OffsetsLO(L._DeviceOp):

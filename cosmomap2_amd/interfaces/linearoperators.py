@@ -190,11 +190,11 @@ class SparseLO(_DeviceOp):
         return D.like_input(out, v)
 
 
-class _TileHandle(object):
+class _TileHandle(_hip.Handle):
     """Owns a cm2_tiles object (tile-bucketed copy of the pointing)."""
 
     def __init__(self, handle):
-        self.h = handle
+        _hip.Handle.__init__(self, "cm2_tiles_destroy", handle)
         info = self._info()
         self.nt, self.nvalid, self.tile_pixels, self.ntiles, self.nitems = [int(v) for v in info[:5]]
         self.half_angle = bool(info[5])
@@ -237,14 +237,6 @@ class _TileHandle(object):
         _hip.call("cm2_tiles_set_pt_order", self.h, mode)
         self.pt_fixed = bool(mode)
         self.pt_mode = mode
-
-    def __del__(self):
-        if getattr(self, "h", None):
-            try:
-                _hip.load().cm2_tiles_destroy(self.h)
-            except Exception:
-                pass
-            self.h = None
 
 
 def _sparse_tiles(P, tile_pixels=None, slice_samples=None):
@@ -437,7 +429,7 @@ def _fuse_chain(chain):
                 changed = True
                 continue
             if i + 2 < n and chain[i + 2] is P \
-                    and isinstance(chain[i + 1], (FilterLO, GroundFilterLO, HWPSSFilterLO, CommonModeFilterLO)) \
+                    and isinstance(chain[i + 1], _TimeFilter) \
                     and _use_tiles(P) and chain[i + 1]._tile_compatible(P):
                 # A = P^T F P, the production operator: tile-order P / P^T around the
                 # time-order filter (two streaming permutations instead of the exact-order
@@ -457,21 +449,6 @@ def _fuse_chain(chain):
 
 
 # ================================================================== noise N^-1 ===
-class _NoiseHandle(object):
-    """Owns a cm2_noise object."""
-
-    def __init__(self, handle):
-        self.h = handle
-
-    def __del__(self):
-        if getattr(self, "h", None):
-            try:
-                _hip.load().cm2_noise_destroy(self.h)
-            except Exception:
-                pass
-            self.h = None
-
-
 def _make_toeplitz(bands, sizes, method=0):
     bands = np.ascontiguousarray(bands, dtype=np.float64)
     nb, lam = bands.shape
@@ -480,7 +457,7 @@ def _make_toeplitz(bands, sizes, method=0):
     h = ctypes.c_void_p()
     _hip.call("cm2_noise_create_toeplitz", ctypes.byref(h), pb, int(lam), ps, int(nb),
               int(method), D.stream())
-    return _NoiseHandle(h)
+    return _hip.Handle("cm2_noise_destroy", h)
 
 
 def _noise_apply(handle, nt, v):
@@ -564,7 +541,7 @@ class BlockLO(blk.BlockDiagonalLinearOperator):
             sz, ps = _as_i64(self._sizes)
             h = ctypes.c_void_p()
             _hip.call("cm2_noise_create_diag", ctypes.byref(h), pv, ps, len(self._sizes))
-            self._noise = _NoiseHandle(h)
+            self._noise = _hip.Handle("cm2_noise_destroy", h)
 
     def _make_blocklist(self):
         if self.isoffdiag:
@@ -953,20 +930,6 @@ def filter_plan(subscans, tstart, nsamples, nbolos, poly_order, legendres):
     return starts, lens, table_off, table
 
 
-class _FilterHandle(object):
-    def __init__(self, handle, keep):
-        self.h = handle
-        self.keep = keep                   # tensors the C side borrows
-
-    def __del__(self):
-        if self.h:
-            try:
-                _hip.load().cm2_filter_destroy(self.h)
-            except Exception:
-                pass
-            self.h = None
-
-
 def _flags_match(op, P):
     """The tile order has no slot for the samples ``P`` flags; a time-domain operator may run there only
     if it flags exactly the same samples (the reference passes ``P.pairs``).  Cached on ``op`` per ``P``."""
@@ -979,7 +942,41 @@ def _flags_match(op, P):
     return cache[1]
 
 
-class FilterLO(_DeviceOp):
+def _size(a):
+    return int(a.numel()) if D.is_tensor(a) else int(np.size(a))
+
+
+def _dims(a):
+    return int(a.dim()) if D.is_tensor(a) else int(np.ndim(a))
+
+
+class _TimeFilter(_DeviceOp):
+    """Base of the filters of a time stream of ``self.n`` samples: the length check of an input, the matvec of
+    the classes that are one library call ``_ENTRY(handle, in, out, stream)`` on ``self._handle``, and the rule
+    under which the filter may stand between a tile-order ``P`` and ``P^T``."""
+    _ENTRY = None
+
+    def _input(self, d):
+        x = D.f64(d)
+        if x.numel() != self.n:
+            raise lp.ShapeError("time-domain vector has %d entries, expected %d" % (x.numel(), self.n))
+        return x
+
+    def mult(self, d):
+        x = self._input(d)
+        out = D.empty(self.n)
+        _hip.call(self._ENTRY, self._handle.h, D.ptr(x), D.ptr(out), D.stream())
+        return D.like_input(out, d)
+
+    def _apply_all(self, d):
+        """The operator's own matvec on a device vector (used by the tile-order chain)."""
+        return self.mult(d)
+
+    def _tile_compatible(self, P):
+        return _flags_match(self, P)
+
+
+class FilterLO(_TimeFilter):
     """
     Sub-scan filter of a time stream (reference: linearoperators.py:94-283).
 
@@ -1052,7 +1049,7 @@ class FilterLO(_DeviceOp):
         _hip.call("cm2_filter_create", ctypes.byref(handle), self.n, int(starts.size), p(starts),
                   p(lens), D.ptr(self._d_pix), int(order), p(toff), p(table),
                   0 if table is None else int(table.size), D.stream())
-        h = self._handles[order] = _FilterHandle(handle, self._d_pix)
+        h = self._handles[order] = _hip.Handle("cm2_filter_destroy", handle, keep=self._d_pix)
         return h
 
     def filter_info(self):
@@ -1062,10 +1059,7 @@ class FilterLO(_DeviceOp):
                     skipped=info[4], unflagged=info[5], flagged=info[6])
 
     def _apply(self, order, d):
-        x = D.f64(d)
-        if x.numel() != self.n:
-            raise lp.ShapeError("time-domain vector has %d entries, expected %d"
-                                % (x.numel(), self.n))
+        x = self._input(d)
         out = D.empty(self.n)
         _hip.call("cm2_filter_apply", self._plan_for(order).h, D.ptr(x), D.ptr(out), D.stream())
         return D.like_input(out, d)
@@ -1075,11 +1069,7 @@ class FilterLO(_DeviceOp):
         return self._apply(0, d)
 
     def _apply_all(self, d):
-        """The operator's own matvec on a device vector (used by the tile-order chain)."""
         return self._apply(self.poly_order, d)
-
-    def _tile_compatible(self, P):
-        return _flags_match(self, P)
 
     def _apply_tiles(self, T, d_in_tb, d_out_tb):
         """Filter a TOD held in the tile-bucketed order ``T``; False if the chunks do not fit
@@ -1099,15 +1089,14 @@ class FilterLO(_DeviceOp):
 
 
 # ============================================================== GroundFilterLO ===
-class _GroundSums(object):
+class _GroundSums(_hip.Handle):
     """Owns a cm2_ground_sums handle: the order-independent bin sums of include/cosmomap2.h (f2b)."""
 
     def __init__(self, nbins):
-        self.h = None
         self.nbins = int(nbins)
         h = ctypes.c_void_p()
         _hip.call("cm2_ground_sums_create", ctypes.byref(h), self.nbins, D.stream())
-        self.h = h
+        _hip.Handle.__init__(self, "cm2_ground_sums_destroy", h)
 
     def info(self):
         info = (ctypes.c_int64 * 4)()
@@ -1120,16 +1109,8 @@ class _GroundSums(object):
                   D.stream())
         return sums
 
-    def __del__(self):
-        if getattr(self, "h", None):
-            try:
-                _hip.load().cm2_ground_sums_destroy(self.h)
-            except Exception:
-                pass
-            self.h = None
 
-
-class GroundFilterLO(_DeviceOp):
+class GroundFilterLO(_TimeFilter):
     """
     Ground-template filter ``v - G (G^T G)^-1 G^T v`` (reference: linearoperators.py:24-61):
     ``ground[t]`` is the azimuth bin of sample t (-1 = none), ``G`` the pol=1 pointing
@@ -1163,10 +1144,7 @@ class GroundFilterLO(_DeviceOp):
         return sums
 
     def mult(self, v):
-        x = D.f64(v)
-        if x.numel() != self.n:
-            raise lp.ShapeError("time-domain vector has %d entries, expected %d"
-                                % (x.numel(), self.n))
+        x = self._input(v)
         binned = self._invGtG.mult(self._bin_sums(x))
         out = D.empty(self.n)
         _hip.call("cm2_ground_subtract", self.n, D.ptr(self._G._d_pix), D.ptr(binned), D.ptr(x),
@@ -1221,6 +1199,27 @@ class GroundFilterLO(_DeviceOp):
                                              symmetric=True)
 
 
+# ===================================================== the fit filters' shared parts ===
+def _edges(N, parts, part, length, total):
+    """Edges ``0 = e_0 < ... < e_n = N`` of the parts of ``N >= 1`` items (int64).  ``parts=None``: one part.  An
+    int: parts of that many items, the last one shorter when it does not divide ``N``.  A 1-D array: the edges
+    themselves, checked.  ``part``, ``length``, ``total``: the nouns of the messages."""
+    if parts is None:
+        return np.array([0, N], dtype=np.int64)
+    if np.ndim(parts) == 0:
+        n = int(parts)
+        if n < 1 or n != parts:
+            raise ValueError("the %s must be a positive integer, got %r" % (length, parts))
+        return np.append(np.arange(0, N, n, dtype=np.int64), np.int64(N))
+    e = np.asarray(parts)
+    if e.ndim != 1 or e.size < 2 or not np.issubdtype(e.dtype, np.integer):
+        raise lp.ShapeError("%s edges must be a 1-D integer array of at least two entries" % part)
+    e = np.ascontiguousarray(e, dtype=np.int64)
+    if e[0] != 0 or e[-1] != N or np.any(np.diff(e) <= 0):
+        raise ValueError("%s edges must ascend strictly from 0 to %s=%d" % (part, total, N))
+    return e
+
+
 # =============================================================== HWPSSFilterLO ===
 HWPSS_MAX_HARM = 8           # CM2_HWPSS_MAX_HARM of include/cosmomap2.h
 
@@ -1233,37 +1232,10 @@ def hwpss_plan(ns, chunks=None):
     ns = int(ns)
     if ns < 1:
         raise ValueError("ns must be >= 1, got %d" % ns)
-    if chunks is None:
-        return np.array([0, ns], dtype=np.int64)
-    if np.ndim(chunks) == 0:
-        n = int(chunks)
-        if n < 1 or n != chunks:
-            raise ValueError("the chunk length must be a positive integer, got %r" % (chunks,))
-        return np.append(np.arange(0, ns, n, dtype=np.int64), np.int64(ns))
-    e = np.asarray(chunks)
-    if e.ndim != 1 or e.size < 2 or not np.issubdtype(e.dtype, np.integer):
-        raise lp.ShapeError("chunk edges must be a 1-D integer array of at least two entries")
-    e = np.ascontiguousarray(e, dtype=np.int64)
-    if e[0] != 0 or e[-1] != ns or np.any(np.diff(e) <= 0):
-        raise ValueError("chunk edges must ascend strictly from 0 to ns=%d" % ns)
-    return e
+    return _edges(ns, chunks, "chunk", "chunk length", "ns")
 
 
-class _HWPSSHandle(object):
-    def __init__(self, handle, keep):
-        self.h = handle
-        self.keep = keep                   # the flag tensor the C side borrows
-
-    def __del__(self):
-        if self.h:
-            try:
-                _hip.load().cm2_hwpss_destroy(self.h)
-            except Exception:
-                pass
-            self.h = None
-
-
-class HWPSSFilterLO(_DeviceOp):
+class HWPSSFilterLO(_TimeFilter):
     """
     HWP-synchronous signal filter: per detector and chunk, fit the harmonics ``1, cos(n chi), sin(n chi)``,
     ``n = 1..nharm``, of the half-wave plate angle to the unflagged samples and subtract them
@@ -1276,6 +1248,7 @@ class HWPSSFilterLO(_DeviceOp):
     samples, or whose harmonics are collinear on them (Cholesky pivot <= 2^-10 of its diagonal entry), is skipped:
     its output and its coefficients are 0; ``filter_info()`` counts them.  Flagged samples are 0 in the output.
     """
+    _ENTRY = "cm2_hwpss_apply"
 
     def __init__(self, chi, pix_samples, ndet=1, nharm=4, chunks=None):
         if int(nharm) != nharm or not 1 <= int(nharm) <= HWPSS_MAX_HARM:
@@ -1284,15 +1257,13 @@ class HWPSSFilterLO(_DeviceOp):
             raise ValueError("ndet must be a positive integer, got %r" % (ndet,))
         self.nharm, self.ndet = int(nharm), int(ndet)
         self.K = 2 * self.nharm + 1
-        size = lambda a: int(a.numel()) if D.is_tensor(a) else int(np.size(a))
-        dims = lambda a: int(a.dim()) if D.is_tensor(a) else int(np.ndim(a))
-        if dims(chi) != 1 or size(chi) < 1:
+        if _dims(chi) != 1 or _size(chi) < 1:
             raise lp.ShapeError("chi must be a 1-D array of at least one plate angle")
-        self.ns = size(chi)
+        self.ns = _size(chi)
         self.n = self.ndet * self.ns
-        if size(pix_samples) != self.n:
+        if _size(pix_samples) != self.n:
             raise lp.ShapeError("pix_samples has %d entries, expected ndet * len(chi) = %d"
-                                % (size(pix_samples), self.n))
+                                % (_size(pix_samples), self.n))
         self.edges = hwpss_plan(self.ns, chunks)
         self.nchunks = int(self.edges.size) - 1
         D.require_gpu()
@@ -1301,7 +1272,7 @@ class HWPSSFilterLO(_DeviceOp):
         handle = ctypes.c_void_p()
         _hip.call("cm2_hwpss_create", ctypes.byref(handle), self.ns, self.ndet, self.nchunks,
                   self.edges.ctypes.data_as(_I64P), D.ptr(d_chi), D.ptr(self._d_pix), self.nharm, D.stream())
-        self._handle = _HWPSSHandle(handle, self._d_pix)
+        self._handle = _hip.Handle("cm2_hwpss_destroy", handle, keep=self._d_pix)
         super(HWPSSFilterLO, self).__init__(nargin=self.n, nargout=self.n, matvec=self.mult, symmetric=True)
 
     def filter_info(self):
@@ -1309,20 +1280,6 @@ class HWPSSFilterLO(_DeviceOp):
         _hip.call("cm2_hwpss_info", self._handle.h, info)
         return dict(zip(("ns", "ndet", "nchunks", "nharm", "fitted", "skipped_few", "skipped_pivot",
                          "segment", "segments"), [int(v) for v in info]))
-
-    def _input(self, d):
-        x = D.f64(d)
-        if x.numel() != self.n:
-            raise lp.ShapeError("time-domain vector has %d entries, expected %d" % (x.numel(), self.n))
-        return x
-
-    def mult(self, d):
-        x = self._input(d)
-        out = D.empty(self.n)
-        _hip.call("cm2_hwpss_apply", self._handle.h, D.ptr(x), D.ptr(out), D.stream())
-        return D.like_input(out, d)
-
-    _apply_all = mult
 
     def coefficients(self, d):
         """The fitted coefficients ``[ndet, nchunks, 2 nharm + 1]`` of ``d`` (zeros for a skipped unit), in the
@@ -1338,9 +1295,6 @@ class HWPSSFilterLO(_DeviceOp):
         _hip.call("cm2_hwpss_tables", self._handle.h, D.ptr(c), D.ptr(s), D.stream())
         return c, s
 
-    def _tile_compatible(self, P):
-        return _flags_match(self, P)
-
 
 # ========================================================== CommonModeFilterLO ===
 CMODE_MAX_K = 10             # CM2_CMODE_MAX_K of include/cosmomap2.h
@@ -1354,21 +1308,7 @@ def cmode_groups(ndet, groups=None):
     it does not divide ``ndet``.  A 1-D array: the edges themselves, checked."""
     if int(ndet) != ndet or int(ndet) < 1:
         raise ValueError("ndet must be a positive integer, got %r" % (ndet,))
-    ndet = int(ndet)
-    if groups is None:
-        return np.array([0, ndet], dtype=np.int64)
-    if np.ndim(groups) == 0:
-        n = int(groups)
-        if n < 1 or n != groups:
-            raise ValueError("the group size must be a positive integer, got %r" % (groups,))
-        return np.append(np.arange(0, ndet, n, dtype=np.int64), np.int64(ndet))
-    e = np.asarray(groups)
-    if e.ndim != 1 or e.size < 2 or not np.issubdtype(e.dtype, np.integer):
-        raise lp.ShapeError("group edges must be a 1-D integer array of at least two entries")
-    e = np.ascontiguousarray(e, dtype=np.int64)
-    if e[0] != 0 or e[-1] != ndet or np.any(np.diff(e) <= 0):
-        raise ValueError("group edges must ascend strictly from 0 to ndet=%d" % ndet)
-    return e
+    return _edges(int(ndet), groups, "group", "group size", "ndet")
 
 
 def focalplane_modes(xy, order, groups=None):
@@ -1399,21 +1339,7 @@ def focalplane_modes(xy, order, groups=None):
     return np.ascontiguousarray(np.stack(cols, axis=1))
 
 
-class _CModeHandle(object):
-    def __init__(self, handle, keep):
-        self.h = handle
-        self.keep = keep                   # the flag tensor the C side borrows
-
-    def __del__(self):
-        if self.h:
-            try:
-                _hip.load().cm2_cmode_destroy(self.h)
-            except Exception:
-                pass
-            self.h = None
-
-
-class CommonModeFilterLO(_DeviceOp):
+class CommonModeFilterLO(_TimeFilter):
     """
     Common-mode filter: per group of detectors and time sample, fit ``K`` templates ``Phi[k, :]`` across the
     unflagged detectors and subtract them (``M - M Phi G^-1 Phi^T M``, symmetric and idempotent;
@@ -1429,11 +1355,11 @@ class CommonModeFilterLO(_DeviceOp):
     output.
     """
     CLASSES = ("fitted", "empty", "few", "pivot")
+    _ENTRY = "cm2_cmode_apply"
 
     def __init__(self, pix_samples, ndet, modes=None, groups=None):
         self.edges = cmode_groups(ndet, groups)
         self.ndet, self.ngroups = int(ndet), int(self.edges.size) - 1
-        size = lambda a: int(a.numel()) if D.is_tensor(a) else int(np.size(a))
         if modes is None:
             modes = np.ones((self.ndet, 1))
         shape = tuple(modes.shape) if D.is_tensor(modes) else np.shape(modes)
@@ -1442,7 +1368,7 @@ class CommonModeFilterLO(_DeviceOp):
         if not 1 <= shape[1] <= CMODE_MAX_K:
             raise ValueError("modes has K = %d templates, K must be in [1, %d]" % (shape[1], CMODE_MAX_K))
         self.K = int(shape[1])
-        n = size(pix_samples)
+        n = _size(pix_samples)
         if n < self.ndet or n % self.ndet:
             raise lp.ShapeError("pix_samples has %d entries, not a positive multiple of ndet = %d" % (n, self.ndet))
         self.n, self.ns = n, n // self.ndet
@@ -1452,27 +1378,13 @@ class CommonModeFilterLO(_DeviceOp):
         handle = ctypes.c_void_p()
         _hip.call("cm2_cmode_create", ctypes.byref(handle), self.ns, self.ndet, self.ngroups,
                   self.edges.ctypes.data_as(_I64P), self.K, D.ptr(d_modes), D.ptr(self._d_pix), D.stream())
-        self._handle = _CModeHandle(handle, self._d_pix)
+        self._handle = _hip.Handle("cm2_cmode_destroy", handle, keep=self._d_pix)
         super(CommonModeFilterLO, self).__init__(nargin=self.n, nargout=self.n, matvec=self.mult, symmetric=True)
 
     def filter_info(self):
         info = (ctypes.c_int64 * 8)()
         _hip.call("cm2_cmode_info", self._handle.h, info)
         return dict(zip(("ns", "ndet", "ngroups", "K") + self.CLASSES, [int(v) for v in info]))
-
-    def _input(self, d):
-        x = D.f64(d)
-        if x.numel() != self.n:
-            raise lp.ShapeError("time-domain vector has %d entries, expected %d" % (x.numel(), self.n))
-        return x
-
-    def mult(self, d):
-        x = self._input(d)
-        out = D.empty(self.n)
-        _hip.call("cm2_cmode_apply", self._handle.h, D.ptr(x), D.ptr(out), D.stream())
-        return D.like_input(out, d)
-
-    _apply_all = mult
 
     def coefficients(self, d):
         """The fitted coefficients ``[ngroups, K, ns]`` of ``d`` (zeros for a skipped unit); nothing is
@@ -1488,6 +1400,3 @@ class CommonModeFilterLO(_DeviceOp):
         out = D.empty(self.ngroups * self.ns, torch.uint8)
         _hip.call("cm2_cmode_status", self._handle.h, D.ptr(out))
         return D.to_host(out).reshape(self.ngroups, self.ns)
-
-    def _tile_compatible(self, P):
-        return _flags_match(self, P)

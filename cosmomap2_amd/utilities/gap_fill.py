@@ -126,11 +126,10 @@ def _check_nedge(nedge):
     return nedge
 
 
-class _Gaps(object):
+class _Gaps(_hip.Handle):
     """Owns a cm2_gaps handle and the device flags it reads."""
 
     def __init__(self, flags, sizes, a0=None):
-        self.h = None
         self.flags, kind = _flags_to_dev(flags)
         sz = np.ascontiguousarray(sizes, dtype=np.int64)
         pa = None
@@ -140,7 +139,7 @@ class _Gaps(object):
         h = ctypes.c_void_p()
         _hip.call("cm2_gaps_create", ctypes.byref(h), D.ptr(self.flags), kind, int(sum(sizes)),
                   sz.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), len(sizes), pa, D.stream())
-        self.h = h
+        _hip.Handle.__init__(self, "cm2_gaps_destroy", h)
 
     def info(self):
         info = (ctypes.c_int64 * 5)()
@@ -158,14 +157,6 @@ class _Gaps(object):
     def fill_linear(self, d, nedge, out):
         return _run_fill(d, out, lambda x, y: _hip.call("cm2_gaps_fill_linear", self.h, D.ptr(x), D.ptr(y), nedge,
                                                         D.stream()))
-
-    def __del__(self):
-        if getattr(self, "h", None):
-            try:
-                _hip.load().cm2_gaps_destroy(self.h)
-            except Exception:
-                pass
-            self.h = None
 
 
 def _run_fill(d, out, run):

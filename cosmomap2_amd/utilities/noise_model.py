@@ -120,25 +120,18 @@ def _check_psd(psd):
     return shape[0], L
 
 
-class _Psd(object):
+class _Psd(_hip.Handle):
     """Owns a cm2_psd handle (plan and workspace of one nperseg)."""
 
     def __init__(self, L, detrend, work_bytes):
-        self.h = ctypes.c_void_p()
-        _hip.call("cm2_psd_create", ctypes.byref(self.h), int(L), int(detrend), int(work_bytes or 0), D.stream())
+        h = ctypes.c_void_p()
+        _hip.call("cm2_psd_create", ctypes.byref(h), int(L), int(detrend), int(work_bytes or 0), D.stream())
+        _hip.Handle.__init__(self, "cm2_psd_destroy", h)
 
     def info(self):
         info = (ctypes.c_int64 * 3)()
         _hip.call("cm2_psd_info", self.h, info)
         return dict(nperseg=int(info[0]), segments_per_batch=int(info[1]), work_bytes=int(info[2]))
-
-    def __del__(self):
-        if getattr(self, "h", None):
-            try:
-                _hip.load().cm2_psd_destroy(self.h)
-            except Exception:
-                pass
-            self.h = None
 
 
 def noise_psd(d, blocksize, nperseg, fsample=1.0, detrend="constant", work_bytes=None):

@@ -165,7 +165,7 @@ def _check_draw_args(nt, realization, out, add, scale):
     return realization, bool(add), scale
 
 
-class NoiseSimulator(object):
+class NoiseSimulator(_hip.Handle):
     """
     Coloured noise for the blocks ``blocksize`` with the one-sided PSD ``psd``: ``[1, L/2+1]`` (shared by
     all blocks) or ``[nb, L/2+1]``, filtered with :func:`noise_filter_bands` of length ``lam``.
@@ -180,7 +180,7 @@ class NoiseSimulator(object):
     def __init__(self, blocksize, psd, lam, fsample=1.0, seed=0, first_block=0, nt=None):
         sizes, nb_psd, L, lam, fs, self.seed, self.first_block = _check_sim_args(blocksize, psd, lam, fsample, seed,
                                                                                  first_block, nt)
-        self.sizes, self.nt, self.lam, self.h = sizes, sum(sizes), lam, None
+        self.sizes, self.nt, self.lam = sizes, sum(sizes), lam
         D.require_gpu()
         g = np.ascontiguousarray(D.to_host(noise_filter_bands(psd, lam, fs)), dtype=np.float64)
         if nb_psd == 1 and len(sizes) > 1:
@@ -191,7 +191,7 @@ class NoiseSimulator(object):
         _hip.call("cm2_noise_sim_create", ctypes.byref(h), g.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), lam,
                   sz.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), len(sizes), self.seed, self.first_block,
                   D.stream())
-        self.h = h
+        _hip.Handle.__init__(self, "cm2_noise_sim_destroy", h)
         self._host_out = None          # device buffer behind a NumPy `out`, made on first use
 
     def info(self):
@@ -223,14 +223,6 @@ class NoiseSimulator(object):
         else:
             out[:] = y
         return out
-
-    def __del__(self):
-        if getattr(self, "h", None):
-            try:
-                _hip.load().cm2_noise_sim_destroy(self.h)
-            except Exception:
-                pass
-            self.h = None
 
 
 def simulate_noise(blocksize, psd, lam, seed, realization=0, fsample=1.0, first_block=0, nt=None, out=None,

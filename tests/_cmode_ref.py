@@ -28,15 +28,17 @@ from types import SimpleNamespace
 
 import numpy as np
 
+import _fit_ref as F
 import _vector_ref as V
 
 LD, U53, _ld = V.LD, V.U53, V._ld
 bits, assert_bit_equal, pow2_at_least = V.bits, V.assert_bit_equal, V.pow2_at_least
+cholesky, solve, excess, assert_accepted = F.cholesky, F.solve, F.excess, F.assert_accepted
 
 THREADS = 256                        # kThreads of cm2_cmode_policy.h
 MAX_K = 10                           # kMaxK, CM2_CMODE_MAX_K
-TAU = 2.0 ** -10                     # CM2_CMODE_TAU
-NEAR = 2.0 ** -20                    # no tested pivot ratio within TAU (1 +- NEAR)
+TAU = F.TAU                          # CM2_CMODE_TAU
+NEAR = F.NEAR                        # no tested pivot ratio within TAU (1 +- NEAR)
 FITTED, EMPTY, FEW, PIVOT = 0, 1, 2, 3
 
 # largest |cmode_f64 - cmode_ref| / (2^-53 S) over outputs and coefficients of the shared cases, rounded up to one
@@ -59,15 +61,7 @@ def c_bound(nd, K):
     return c_count(nd, K) * HEADROOM
 
 
-def cmode_groups(ndet, groups):
-    """edges, as cosmomap2_amd.interfaces.cmode_groups defines them (restated: the reference must not import the
-    code under test)"""
-    ndet = int(ndet)
-    if groups is None:
-        return np.array([0, ndet], dtype=np.int64)
-    if np.ndim(groups) == 0:
-        return np.append(np.arange(0, ndet, int(groups), dtype=np.int64), ndet)
-    return np.asarray(groups, dtype=np.int64)
+cmode_groups = F.edges               # (ndet, groups) -> edges, as cosmomap2_amd.interfaces.cmode_groups defines them
 
 
 def focalplane_modes(xy, order, groups=None):
@@ -104,64 +98,13 @@ def policy_status(ns, ndet, edges, K):
         return 1
     if ns < 1 or ndet < 1 or G < 1:
         return 2
-    if G > ndet or edges[0] != 0 or edges[-1] != ndet or any(b <= a for a, b in zip(edges[:-1], edges[1:])):
+    if not F.edges_ok(edges, ndet):
         return 3
     if ndet >= 1 << 31 or ndet > (1 << 46) // ns:
         return 4
     if G > ((1 << 31) - 1) // blocks_per_group(ns):
         return 4
     return 0
-
-
-# -------------------------------------- Cholesky with the pivot rule, over the units ----
-def cholesky(G, dtype):
-    """Row-by-row factor of G[n, K, K] (its lower triangle) in `dtype`, the operation order written at the top of
-    cm2_hwpss.hip.  -> SimpleNamespace(L [n, K, K], failed [n]: a pivot p_j <= TAU G_jj was met, ratio [n]: the
-    smallest p_j / G_jj tested -- the factorisation stops at the first failed pivot --, near [n]: a tested ratio
-    lies within TAU (1 +- NEAR)).  What follows a failed pivot in L is not meaningful."""
-    A = np.array(G, dtype=dtype)
-    n, K = A.shape[0], A.shape[1]
-    failed, near = np.zeros(n, dtype=bool), np.zeros(n, dtype=bool)
-    worst = np.full(n, np.inf)
-    tau = dtype(TAU)
-    with np.errstate(all="ignore"):
-        for j in range(K):
-            gjj = A[:, j, j].copy()
-            p = gjj.copy()
-            for k in range(j):
-                p = p - A[:, j, k] * A[:, j, k]
-            ratio = np.where(gjj != 0, p / np.where(gjj != 0, gjj, 1), 0)
-            ratio = np.where(np.isnan(ratio), 0, ratio)
-            alive = ~failed
-            worst = np.where(alive, np.minimum(worst, ratio.astype(np.float64)), worst)
-            near |= alive & (np.abs(ratio - tau) <= tau * dtype(NEAR))
-            failed |= alive & ~(p > tau * gjj)
-            ljj = np.sqrt(p)
-            A[:, j, j] = ljj
-            for i in range(j + 1, K):
-                t = A[:, i, j].copy()
-                for k in range(j):
-                    t = t - A[:, i, k] * A[:, j, k]
-                A[:, i, j] = t / ljj
-    return SimpleNamespace(L=A, failed=failed, ratio=worst, near=near)
-
-
-def solve(L, b):
-    """the two triangular solves of L[n, K, K], b[n, K], the known terms subtracted in ascending index order"""
-    K = L.shape[1]
-    y = np.array(b, dtype=L.dtype)
-    with np.errstate(all="ignore"):
-        for i in range(K):
-            a = y[:, i].copy()
-            for k in range(i):
-                a = a - L[:, i, k] * y[:, k]
-            y[:, i] = a / L[:, i, i]
-        for i in range(K - 1, -1, -1):
-            a = y[:, i].copy()
-            for k in range(i + 1, K):
-                a = a - L[:, k, i] * y[:, k]
-            y[:, i] = a / L[:, i, i]
-    return y
 
 
 def classes(m, K, failed):
@@ -267,22 +210,6 @@ def c_coeffs(ns, edges, K):
     """c per coefficient [G, K, ns]"""
     per = np.array([c_bound(n, K) for n in np.diff(edges)])
     return np.broadcast_to(per[:, None, None], (len(per), K, ns)).copy()
-
-
-def excess(got, ref, S, c):
-    return V.excess(got, ref, _ld(S).reshape(-1) * _ld(c).reshape(-1), 1)
-
-
-def assert_accepted(got, f64, ref, S, c, what=""):
-    """element by element: bit-equal to the restatement, or within c 2^-53 S of the reference"""
-    got, f64 = np.asarray(got, dtype=np.float64).reshape(-1), np.asarray(f64, dtype=np.float64).reshape(-1)
-    same = bits(got) == bits(f64)
-    ref, S, c = _ld(ref).reshape(-1), _ld(S).reshape(-1), _ld(c).reshape(-1)
-    if same.all():
-        return 0.0
-    e = excess(got[~same], ref[~same], S[~same], c[~same])
-    assert e <= 1.0, "%s: |got - ref| is %.3g x the bound c 2^-53 S" % (what, e)
-    return e
 
 
 # ---------------------------------------------------------------------- cases ----

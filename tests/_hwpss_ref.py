@@ -27,14 +27,16 @@ from types import SimpleNamespace
 
 import numpy as np
 
+import _fit_ref as F
 import _vector_ref as V
 
 LD, U53, _ld = V.LD, V.U53, V._ld
 bits, assert_bit_equal, pow2_at_least = V.bits, V.assert_bit_equal, V.pow2_at_least
+excess, assert_accepted = F.excess, F.assert_accepted
 
 SEG, THREADS = 4096, 256             # kSeg, kThreads of cm2_hwpss_policy.h
 PER = SEG // THREADS
-TAU = 2.0 ** -10                     # CM2_HWPSS_TAU
+TAU = F.TAU                          # CM2_HWPSS_TAU
 MAX_HARM = 8
 PIVOT_OK, PIVOT_GONE = 2.0 ** -5, 2.0 ** -40
 
@@ -61,16 +63,7 @@ def c_bound(nseg, H):
     return c_count(nseg, H) * HEADROOM
 
 
-def hwpss_plan(ns, chunks):
-    """edges, as cosmomap2_amd.interfaces.hwpss_plan defines them (restated: the reference must not import the
-    code under test)"""
-    ns = int(ns)
-    if chunks is None:
-        return np.array([0, ns], dtype=np.int64)
-    if np.ndim(chunks) == 0:
-        n = int(chunks)
-        return np.append(np.arange(0, ns, n, dtype=np.int64), ns)
-    return np.asarray(chunks, dtype=np.int64)
+hwpss_plan = F.edges                 # (ns, chunks) -> edges, as cosmomap2_amd.interfaces.hwpss_plan defines them
 
 
 def segments_of(edges):
@@ -100,46 +93,14 @@ def templates_f64(c1, s1, H):
 
 # ------------------------------------------------- Cholesky with the pivot rule ----
 def cholesky(G, dtype):
-    """Row-by-row factor in `dtype`, the kernel's operation order.  -> (L or None, smallest pivot ratio met):
-    stops at the first pivot p_j <= TAU G_jj, which is then the ratio returned."""
-    K = G.shape[0]
-    A = np.array(G, dtype=dtype)
-    worst = np.inf
-    for j in range(K):
-        gjj = A[j, j]
-        p = gjj
-        for k in range(j):
-            p = p - A[j, k] * A[j, k]
-        with np.errstate(divide="ignore", invalid="ignore"):
-            ratio = float(p / gjj) if gjj != 0 else 0.0
-        worst = min(worst, ratio if ratio == ratio else 0.0)
-        if not (p > dtype(TAU) * gjj):
-            return None, worst
-        ljj = np.sqrt(p)
-        A[j, j] = ljj
-        for i in range(j + 1, K):
-            v = A[i, j]
-            for k in range(j):
-                v = v - A[i, k] * A[j, k]
-            A[i, j] = v / ljj
-    return np.tril(A), worst
+    """one unit through the batched form of _fit_ref.py -> (L or None when a pivot failed, the smallest pivot
+    ratio tested)"""
+    ch = F.cholesky(np.asarray(G)[None], dtype)
+    return (None if ch.failed[0] else np.tril(ch.L[0])), float(ch.ratio[0])
 
 
 def solve(L, b):
-    """the two triangular solves, the known terms subtracted in ascending index order"""
-    K = L.shape[0]
-    y = np.array(b, dtype=L.dtype)
-    for i in range(K):
-        a = y[i]
-        for k in range(i):
-            a = a - L[i, k] * y[k]
-        y[i] = a / L[i, i]
-    for i in range(K - 1, -1, -1):
-        a = y[i]
-        for k in range(i + 1, K):
-            a = a - L[k, i] * y[k]
-        y[i] = a / L[i, i]
-    return y
+    return F.solve(L[None], np.asarray(b)[None])[0]
 
 
 # --------------------------------------------------------------- the reference ----
@@ -271,22 +232,6 @@ def c_coeffs(ndet, edges, H):
     K = 2 * H + 1
     per = np.repeat([c_bound(n, H) for n in segments_of(edges)], K).reshape(-1, K)
     return np.tile(per[None], (ndet, 1, 1))
-
-
-def excess(got, ref, S, c):
-    return V.excess(got, ref, _ld(S).reshape(-1) * _ld(c).reshape(-1), 1)
-
-
-def assert_accepted(got, f64, ref, S, c, what=""):
-    """element by element: bit-equal to the restatement, or within c 2^-53 S of the reference"""
-    got, f64 = np.asarray(got, dtype=np.float64).reshape(-1), np.asarray(f64, dtype=np.float64).reshape(-1)
-    same = bits(got) == bits(f64)
-    ref, S, c = _ld(ref).reshape(-1), _ld(S).reshape(-1), _ld(c).reshape(-1)
-    if same.all():
-        return 0.0
-    e = excess(got[~same], ref[~same], S[~same], c[~same])
-    assert e <= 1.0, "%s: |got - ref| is %.3g x the bound c 2^-53 S" % (what, e)
-    return e
 
 
 # ---------------------------------------------------------------------- cases ----
