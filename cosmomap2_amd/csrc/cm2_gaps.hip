@@ -568,6 +568,7 @@ extern "C" int cm2_gaps_fill_linear(const cm2_gaps *g, const double *d_d, double
 {
     CM2_CHECK(g && d_d && d_out, "cm2_gaps_fill_linear: NULL argument");
     CM2_CHECK(nedge >= 1, "cm2_gaps_fill_linear: nedge=%lld < 1", (long long)nedge);
+    if (nedge > g->nt) nedge = g->nt;               // no window reaches further, and s - nedge, e + nedge cannot wrap
     hipStream_t stream = as_stream(stream_);
     if (int rc = gaps_copy_valid(g, d_d, d_out, stream)) return rc;
     if (!g->ng) return 0;

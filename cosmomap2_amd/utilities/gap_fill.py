@@ -34,7 +34,7 @@ a solve; a wholly flagged block gets ``n`` (zeros without ``sim``).
 valid samples among the ``nedge`` samples before ``s`` inside the block and ``R`` the same after the run; a side
 without a valid sample takes the other side's level, both without: 0.  Sample ``s + k`` becomes
 ``L + (R - L) (k + 1) / (len + 1)``; valid samples are copied bit for bit.  A run that crosses a block boundary is
-two runs.
+two runs.  ``nedge`` above the stream's length means the stream's length.
 
 ``d`` and ``out`` are float64 tensors in HBM or NumPy arrays.  Every argument is checked before the GPU is
 touched (``ValueError``); without a GPU a valid call raises ``HipError`` like every operator constructor.  On
@@ -183,7 +183,7 @@ def fill_gaps_linear(d, flags, blocksize, nedge=32, out=None):
     nt = _check_flags(flags)
     _check_tod("d", d, nt)
     sizes = _block_sizes(blocksize, nt)
-    nedge = _check_nedge(nedge)
+    nedge = min(_check_nedge(nedge), nt)            # no edge window reaches further; the C side takes an int64
     _check_out(out, nt)
     D.require_gpu()
     return _Gaps(flags, sizes).fill_linear(d, nedge, out)

@@ -791,7 +791,8 @@ int cm2_gaps_finish(const cm2_gaps *g, const double *d_d, const double *d_n, con
 /* Linear fill: for each run [s, s + len) inside its block, L = mean of the valid samples among the nedge samples
  * before s inside the block, R = the same for the nedge samples after the run, each summed in time order by one
  * thread; a side without a valid sample takes the other side's level, both without: 0.  d_out[s + k] =
- * L + (R - L) (k + 1) / (len + 1); valid samples are copied bit for bit (d_out == d_d: left where they are). */
+ * L + (R - L) (k + 1) / (len + 1); valid samples are copied bit for bit (d_out == d_d: left where they are).
+ * nedge >= 1; a value above nt means nt. */
 int cm2_gaps_fill_linear(const cm2_gaps *g, const double *d_d, double *d_out, int64_t nedge, void *stream);
 
 /* The gap-aware normal operator: one unknown per flagged sample.  With E the nt x ng matrix that has a one at
