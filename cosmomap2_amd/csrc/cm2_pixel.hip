@@ -299,6 +299,9 @@ extern "C" int cm2_pixel_compact(int64_t npix, const uint8_t *d_keep, int32_t *d
                                  int64_t *h_new_npix, void *stream_)
 {
     CM2_CHECK(d_keep && d_old2new && h_new_npix, "cm2_pixel_compact: NULL argument");
+    // element npix - 1 of both arrays is read back below
+    CM2_CHECK(npix >= 1 && npix < (int64_t)0x7FFFFFFF, "cm2_pixel_compact: npix=%lld out of range",
+              (long long)npix);
     hipStream_t stream = as_stream(stream_);
     DevTemp<int32_t> flags;
     DevTemp<char> d_temp;
@@ -562,13 +565,14 @@ extern "C" int cm2_cutsky_to_fullsky(int pol, int64_t npix, const int64_t *d_obs
     CM2_CHECK(pol >= 1 && pol <= 3, "cm2_cutsky_to_fullsky: pol=%d", pol);
     CM2_CHECK(npix >= 0 && nfull >= 0, "cm2_cutsky_to_fullsky: negative size");
     hipStream_t st = cm2::as_stream(stream);
-    if (nfull) {
-        CM2_CHECK(d_full, "cm2_cutsky_to_fullsky: null output");
-        CM2_HIP(hipMemsetAsync(d_full, 0, sizeof(double) * (size_t)pol * nfull, st));
+    // every argument is validated before the first write: a refused call leaves d_full untouched
+    CM2_CHECK(d_full || nfull == 0, "cm2_cutsky_to_fullsky: null output");
+    if (npix > 0) {
+        CM2_CHECK(d_obspix && d_map, "cm2_cutsky_to_fullsky: null input");
+        if (int rc = cm2::check_obspix(npix, d_obspix, nfull, st)) return rc;
     }
+    if (nfull) CM2_HIP(hipMemsetAsync(d_full, 0, sizeof(double) * (size_t)pol * nfull, st));
     if (npix == 0) return 0;
-    CM2_CHECK(d_obspix && d_map, "cm2_cutsky_to_fullsky: null input");
-    if (int rc = cm2::check_obspix(npix, d_obspix, nfull, st)) return rc;
     cm2::k_cut_to_full<<<cm2::grid_for(npix), cm2::kBlock, 0, st>>>(pol, npix, d_obspix, d_map, nfull,
                                                                      d_full);
     CM2_LAUNCH_OK();

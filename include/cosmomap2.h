@@ -297,7 +297,7 @@ int cm2_pixel_mask(int pol, int64_t npix, const double *d_counts, const double *
                    const double *d_sin2, const double *d_sincos, double threshold,
                    uint8_t *d_keep, void *stream);
 /* old2new[p] = rank of p among kept pixels or -1; *h_new_npix = kept count.
- * Same output as the O(Nold*Nm) search at :205-228, by prefix sum.  Synchronises. */
+ * Same output as the O(Nold*Nm) search at :205-228, by prefix sum.  npix >= 1.  Synchronises. */
 int cm2_pixel_compact(int64_t npix, const uint8_t *d_keep, int32_t *d_old2new,
                       int64_t *h_new_npix, void *stream);
 /* d_out[old2new[p]] = d_in[p] for kept pixels (:218-219, :248-251, :280-286). */
@@ -668,7 +668,7 @@ int cm2_cmode_status(const cm2_cmode *h, uint8_t *d_status);
  * ([I | Q | U]); component k of observed pixel i, d_map[pol*i + k], goes to
  * d_full[k*nfull + d_obspix[i]], all other pixels are 0 (reorganize_map,
  * utilities/healpy_functions.py:47-102).  cm2_fullsky_to_cutsky is the inverse gather
- * (full2cutskymap, utilities/IOfiles.py:377-393).  Pixel ids outside [0, nfull) fail. */
+ * (full2cutskymap, utilities/IOfiles.py:377-393).  Pixel ids outside [0, nfull) fail, before anything is written. */
 int cm2_cutsky_to_fullsky(int pol, int64_t npix, const int64_t *d_obspix, const double *d_map,
                           int64_t nfull, double *d_full, void *stream);
 int cm2_fullsky_to_cutsky(int pol, int64_t npix, const int64_t *d_obspix, const double *d_full,
