@@ -10,3 +10,4 @@ from .offset_prior import *                                  # noqa: F401,F403
 from .noise_sim import *                                     # noqa: F401,F403
 from .gap_fill import *                                      # noqa: F401,F403
 from .pointing_expand import *                               # noqa: F401,F403
+from .glitches import *                                      # noqa: F401,F403

@@ -663,6 +663,73 @@ int cm2_cmode_apply(cm2_cmode *h, const double *d_in, double *d_out, void *strea
 int cm2_cmode_fit(cm2_cmode *h, const double *d_in, double *d_coeff, void *stream);
 int cm2_cmode_status(const cm2_cmode *h, uint8_t *d_status);
 
+/* ---- f2e: glitch flags  (GlitchFlagger, flag_glitches, apply_flags) ----------------------------
+ * Flags cosmic-ray hits, short readout jumps and non-finite samples of a time stream from the data: per noise block
+ * a running median is subtracted, the median absolute deviation of the residual gives a robust scale, samples beyond
+ * nsigma scales are hits and every hit grows by a few samples.  No counterpart in the reference: the definition is
+ * the one below.  Every result is an order statistic, a comparison or an integer count, so it does not depend on how
+ * it is computed: the same bits every time, on every layout of threads.
+ * Inputs: d[nt]; noise blocks of sizes[0..nblocks-1] samples adding up to nt (BlockLO's convention); optional flags
+ * in the two encodings of cm2_gaps_create (flag_kind 0: int32, flagged when negative; 1: bytes, flagged when
+ * non-zero; d_flags NULL: nothing flagged); the half-width 1 <= h <= CM2_GLITCH_MAX_HALF_WIDTH, W = 2 h + 1; nsigma
+ * finite and > 0; 0 <= grow <= CM2_GLITCH_MAX_GROW; optionally prev[nt], the class bytes of an earlier pass.
+ * All windows and neighbourhoods are cut at the block boundaries.
+ *  1. usable_i: the sample is not flagged, d_i is finite and prev_i (if given) is neither HIT nor NEAR.
+ *  2. For a usable i the window is the usable j of the same block with |j - i| <= h: m_i >= 1 values, ascending
+ *     v_0 <= ... <= v_{m-1}.  m odd: med_i = v_{(m-1)/2}; m even: med_i = 0.5 v_{m/2-1} + 0.5 v_{m/2} (two exact
+ *     halvings and one addition: no overflow).
+ *  3. r_i = d_i - med_i for a usable i, r_i = 0 otherwise.
+ *  4. m_b = the usable samples of block b.  m_b < W: the block is short and sigma_b = +inf.  Otherwise s_b is the
+ *     order statistic of rank (m_b - 1) / 2 (0-based, the lower median) of |r_i| over the usable samples of the block
+ *     and sigma_b = CM2_GLITCH_MAD_TO_SIGMA s_b, one multiplication.  A sigma given by the caller replaces it.
+ *  5. thr_b = nsigma sigma_b, one multiplication; hit_i: usable_i and |r_i| > thr_b (equality is no hit; sigma_b = 0
+ *     makes every non-zero residual a hit, sigma_b = +inf none).
+ *  6. The class of a sample, the first rule that applies: CM2_GLITCH_INPUT flagged on input; CM2_GLITCH_NONFINITE
+ *     d_i not finite; prev_i where that is HIT or NEAR; CM2_GLITCH_HIT hit_i; CM2_GLITCH_NEAR some hit j != i of the
+ *     same block with |j - i| <= grow; CM2_GLITCH_CLEAN.
+ *  7. counts[b][c], int64: the samples of class c in block b.
+ * Iterating (glitches bias the medians and inflate the scale) is the caller's loop: pass k runs 1-7 with prev = the
+ * classes of pass k - 1.  Which of -0.0 and +0.0 a median returns is not specified; it can change the sign of a
+ * zero residual only.
+ *
+ * cm2_glitch_create copies h_sizes; the handle owns the block tables, the per-block histograms of the selection
+ *   (nblocks x 2048 x 4 bytes) and its per-block state, and no nt-sized buffer.  Allocates and synchronises.
+ * cm2_glitch_info: h_info[6] = nt, nblocks, h, outputs per thread of the median kernel, tier of h (0-3: the window in
+ *   registers, h <= 8 / 16 / 32 / 48; 4: 96 keys in registers, the rest in LDS), bytes owned.
+ * cm2_glitch_residual: d_r = r (definitions 1-3).  One launch.
+ * cm2_glitch_scale: d_sigma[nblocks] = sigma (definition 4) from d_r as cm2_glitch_residual made it with the same
+ *   flags and prev.  Six passes over d_r and the flags (d_in is read only where r = 0), no sort.  Uses the handle's
+ *   histograms: one call at a time per handle.
+ * cm2_glitch_classify: d_class[nt] (one byte each) and d_counts[nblocks][5] (definitions 5-7).  d_class must not be
+ *   d_prev: a workgroup reads prev in the halo of its tile, where another one writes.
+ * cm2_glitch_apply_pix: d_pix[i] = -1 where d_class[i] != 0, in place.
+ * The stream-sized calls allocate nothing and do not synchronise.  Refused with CM2_ERR_ARGUMENT, the outputs (and
+ * *out) untouched: h outside [1, 64]; nt < 1 or nt >= 2^32 - 1 (the limit of cm2_gaps); sizes that are not positive
+ * or do not add up to nt; more than 2^18 blocks; NULL pointers (d_flags and d_prev may be NULL); a flag_kind other
+ * than 0 or 1 with flags given; nsigma not finite or <= 0; grow outside [0, 64]; an output that overlaps an input or
+ * another output. */
+#define CM2_GLITCH_MAD_TO_SIGMA 1.4826
+#define CM2_GLITCH_MAX_HALF_WIDTH 64
+#define CM2_GLITCH_MAX_GROW 64
+#define CM2_GLITCH_CLEAN 0
+#define CM2_GLITCH_INPUT 1
+#define CM2_GLITCH_NONFINITE 2
+#define CM2_GLITCH_HIT 3
+#define CM2_GLITCH_NEAR 4
+typedef struct cm2_glitch cm2_glitch;
+int cm2_glitch_create(cm2_glitch **out, int64_t nt, const int64_t *h_sizes, int64_t nblocks, int half_width,
+                      void *stream);
+int cm2_glitch_destroy(cm2_glitch *h);
+int cm2_glitch_info(const cm2_glitch *h, int64_t *h_info);
+int cm2_glitch_residual(cm2_glitch *h, const double *d_in, const void *d_flags, int flag_kind, const uint8_t *d_prev,
+                        double *d_r, void *stream);
+int cm2_glitch_scale(cm2_glitch *h, const double *d_in, const double *d_r, const void *d_flags, int flag_kind,
+                     const uint8_t *d_prev, double *d_sigma, void *stream);
+int cm2_glitch_classify(cm2_glitch *h, const double *d_in, const double *d_r, const void *d_flags, int flag_kind,
+                        const uint8_t *d_prev, const double *d_sigma, double nsigma, int grow, uint8_t *d_class,
+                        int64_t *d_counts, void *stream);
+int cm2_glitch_apply_pix(int64_t nt, const uint8_t *d_class, int32_t *d_pix, void *stream);
+
 /* ---- f3: solution vector <-> full-sky HEALPix maps -------------------------------
  * cm2_cutsky_to_fullsky: d_full is pol arrays of nfull doubles one after the other
  * ([I | Q | U]); component k of observed pixel i, d_map[pol*i + k], goes to
