@@ -94,6 +94,13 @@ inline bool ranges_overlap(const double *a, int64_t na, const double *b, int64_t
     return x < y + (uintptr_t)nb * sizeof(double) && y < x + (uintptr_t)na * sizeof(double);
 }
 
+// do the bytes [a, a + na) and [b, b + nb) overlap?  (a NULL range overlaps nothing)
+inline bool bytes_overlap(const void *a, uint64_t na, const void *b, uint64_t nb)
+{
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return a && b && x < y + nb && y < x + na;
+}
+
 // hipFuncAttributeMaxDynamicSharedMemorySize is a per-device property of a kernel: granted[] (one
 // static array per kernel instance at the call site) remembers what each device was given, so the
 // runtime is asked once per device and again only when a launch needs more.

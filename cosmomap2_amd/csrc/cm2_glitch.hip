@@ -374,13 +374,6 @@ __global__ __launch_bounds__(kBlock) void k_glitch_apply_pix(int64_t nt, const u
         if (cls[i]) pix[i] = -1;
 }
 
-// do [a, a + na) and [b, b + nb) share a byte?
-inline bool bytes_overlap(const void *a, uint64_t na, const void *b, uint64_t nb)
-{
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-    return a && b && x < y + nb && y < x + na;
-}
-
 }  // namespace
 
 struct cm2_glitch {

@@ -25,7 +25,8 @@ NO_SPILL = [r"\bk_os_real<", r"\bk_P_tiles", r"\bk_Pt_tiles", r"\bk_Pt_hot", r"\
             r"\bk_P_time", r"\bk_Zt_partial_wide", r"\bk_m2_finish_wide", r"\bk_gemm_tn_mfma", r"\bk_panel_gemm_mfma",
             r"\bk_Z_axpy_wide", r"\bk_filter_windows", r"\bk_psd_", r"\bk_bands_",
             r"\bk_rng_fill", r"\bk_sim_interior", r"\bk_gap_", r"\bk_offsets_", r"\bk_oprior_",
-            r"\bk_gsum_", r"\bk_pexp", r"\bk_hwpss_", r"\bk_cmode_", r"\bk_glitch_"]
+            r"\bk_gsum_", r"\bk_pexp", r"\bk_hwpss_", r"\bk_cmode_", r"\bk_glitch_",
+            r"\bk_jump_"]
 
 # kernels that must not spill SGPRs to VGPR lanes either: the overlap-save instantiations the default dispatch
 # reaches below 4 GB of TOD (at 246-254 of 256 VGPRs a lane register spent on spilled scalars is one too many);

@@ -11,3 +11,4 @@ from .noise_sim import *                                     # noqa: F401,F403
 from .gap_fill import *                                      # noqa: F401,F403
 from .pointing_expand import *                               # noqa: F401,F403
 from .glitches import *                                      # noqa: F401,F403
+from .jumps import *                                         # noqa: F401,F403

@@ -730,6 +730,80 @@ int cm2_glitch_classify(cm2_glitch *h, const double *d_in, const double *d_r, co
                         int64_t *d_counts, void *stream);
 int cm2_glitch_apply_pix(int64_t nt, const uint8_t *d_class, int32_t *d_pix, void *stream);
 
+/* ---- f2f: baseline jumps  (JumpCorrector, correct_jumps) ----------------------------------------
+ * Finds the steps in the level of a time stream (flux jumps of the readout, relocks), estimates their heights,
+ * subtracts the accumulated offsets and classes the samples around each step, per noise block.  The glitch flagger
+ * cannot see a step: a running median keeps an edge.  No counterpart in the reference: the definition is the one
+ * below, and every result has the bits it gives, on every run and every layout of threads.
+ * Inputs: d[nt]; noise blocks of sizes[0..nblocks-1] samples adding up to nt (BlockLO's convention), block b the
+ * samples [start_b, end_b); optional flags in the two encodings of cm2_gaps_create (flag_kind 0: int32, flagged when
+ * negative; 1: bytes, flagged when non-zero; d_flags NULL: nothing flagged); optionally prev[nt], class bytes of the
+ * glitch flagger or of an earlier pass, non-zero meaning unusable; the half-window 1 <= w <= CM2_JUMP_MAX_WINDOW;
+ * 1 <= min_count <= w; nsigma finite and > 0; 0 <= radius <= CM2_JUMP_MAX_RADIUS.  Everything is cut at the block
+ * boundaries.  Every operation on doubles named below is rounded once (no fused multiply-add).
+ *  1. usable_j: the sample is not flagged, d_j is finite and prev_j == 0 (or prev is NULL).
+ *  2. Window sum, for j with start_b <= j and j + w <= end_b: S_j = the sum of the usable d_k, k = j .. j + w - 1, in
+ *     ascending k, starting from +0.0; n_j = the number of usable samples among them.  (Adding +0.0 for an unusable
+ *     sample gives the same bits as skipping it.)
+ *  3. Step statistic, for i with start_b + w <= i <= end_b - w: L = S_{i-w}, nL = n_{i-w}, R = S_i, nR = n_i.
+ *     evaluable_i: nL >= min_count, nR >= min_count and t_i = R / nR - L / nL is finite (two divisions, one
+ *     subtraction).  Wherever a position is not evaluable -- every position within w of a block end, every block
+ *     shorter than 2 w -- t_i = +0.0 and noeval_i = 1.
+ *  4. Scale: e_b = the evaluable positions of block b.  e_b < 3: the block is short and sigma_b = +inf.  Otherwise
+ *     sigma_b = CM2_GLITCH_MAD_TO_SIGMA x the order statistic of rank (e_b - 1) / 2 (0-based) of |t_i| over the
+ *     evaluable positions: definition 4 of f2e with d = r = t, the noeval bytes as flags and h = 1.  A sigma given by
+ *     the caller replaces it; it is the scale of t, not of d.
+ *  5. Candidate: evaluable_i and |t_i| > nsigma sigma_b (one multiplication; equality is no candidate).
+ *  6. Jump: a candidate p with no evaluable j of the block, 0 < |j - p| <= w, such that |t_j| > |t_p|, or
+ *     |t_j| == |t_p| and j < p.  Its height is a_p = t_p.
+ *  7. The jump table: the positions of the jumps ascending (index into the stream, int64), their heights, and
+ *     njumps_b per block.  With more jumps than the caller's capacity the true counts are still reported and nothing
+ *     beyond the capacity is written.
+ *  8. Correction: block b has the jumps p_1 < ... < p_k; s_0 = +0.0, s_m = s_{m-1} + a_{p_m}; d_out_i = d_i - s_{m(i)}
+ *     with m(i) = #{p <= i}, for every sample, flagged ones included (a non-finite d_i stays non-finite).
+ *  9. The class of a sample, the first rule that applies: (a) prev_i if non-zero; (b) CM2_JUMP_AT where i is a jump;
+ *     (c) CM2_JUMP_NEAR where some jump p != i of the block has |i - p| <= radius; (d) CM2_JUMP_CLEAN.
+ *     counts[b][3], int64: the samples of block b that rules b-d gave CLEAN, AT, NEAR (those with prev_i are in none).
+ * Iterating is the caller's loop: a jump within w of a larger one is suppressed by rule 6 and shows once the larger one
+ * is removed.  Pass k runs 1-9 on the output of pass k - 1 with the classes of pass k - 1 as prev.
+ *
+ * cm2_jump_create copies h_sizes; the handle owns the block tables, one mark byte per sample, the temporary storage
+ *   of the select that makes the table, and a cm2_glitch of half-width 1 for the scale.  Allocates and synchronises.
+ * cm2_jump_info: h_info[6] = nt, nblocks, w, positions per workgroup, LDS bytes of a workgroup of the statistic kernel,
+ *   bytes owned.
+ * cm2_jump_stat: d_t[nt] and d_noeval[nt] (one byte each), rules 1-3.  One launch.
+ * cm2_jump_scale: d_sigma[nblocks], rule 4, by cm2_glitch_scale: one call at a time per handle.
+ * cm2_jump_find: rules 5-7 and the chain of rule 8.  d_njumps[nblocks + 1] = njumps_b and, last, their sum;
+ *   d_pos[capacity], d_heights[capacity] and d_offsets[capacity] = p, a_p and s_m of the first min(sum, capacity)
+ *   jumps, the rest untouched.  Uses the handle's mark bytes: one call at a time per handle.
+ * cm2_jump_correct: d_out[nt], d_class[nt] and d_counts[nblocks][3] (rules 8 and 9) from the table of cm2_jump_find
+ *   with the same capacity.  d_out may be d_in itself.  With more jumps than the capacity only the first capacity
+ *   ones are applied: the caller has to look at the sum first.
+ * The stream-sized calls allocate nothing and do not synchronise.  Refused with CM2_ERR_ARGUMENT, the outputs (and
+ * *out) untouched: w outside [1, 256]; nt < 1 or nt >= 2^32 - 1; sizes that are not positive or do not add up to nt;
+ * more than 2^18 blocks; NULL pointers (d_flags and d_prev may be NULL); a flag_kind other than 0 or 1 with flags
+ * given; min_count outside [1, w]; nsigma not finite or <= 0; capacity < 1; radius outside [0, 256]; an output that
+ * overlaps an input or another output, except d_out == d_in in cm2_jump_correct. */
+#define CM2_JUMP_MAX_WINDOW 256
+#define CM2_JUMP_MAX_RADIUS 256
+#define CM2_JUMP_CLEAN 0
+#define CM2_JUMP_AT 1
+#define CM2_JUMP_NEAR 2
+typedef struct cm2_jump cm2_jump;
+int cm2_jump_create(cm2_jump **out, int64_t nt, const int64_t *h_sizes, int64_t nblocks, int half_window,
+                    void *stream);
+int cm2_jump_destroy(cm2_jump *h);
+int cm2_jump_info(const cm2_jump *h, int64_t *h_info);
+int cm2_jump_stat(cm2_jump *h, const double *d_in, const void *d_flags, int flag_kind, const uint8_t *d_prev,
+                  int min_count, double *d_t, uint8_t *d_noeval, void *stream);
+int cm2_jump_scale(cm2_jump *h, const double *d_t, const uint8_t *d_noeval, double *d_sigma, void *stream);
+int cm2_jump_find(cm2_jump *h, const double *d_t, const uint8_t *d_noeval, const double *d_sigma, double nsigma,
+                  int64_t capacity, int64_t *d_pos, double *d_heights, double *d_offsets, int64_t *d_njumps,
+                  void *stream);
+int cm2_jump_correct(cm2_jump *h, const double *d_in, const uint8_t *d_prev, const int64_t *d_pos,
+                     const double *d_offsets, const int64_t *d_njumps, int64_t capacity, int radius, double *d_out,
+                     uint8_t *d_class, int64_t *d_counts, void *stream);
+
 /* ---- f3: solution vector <-> full-sky HEALPix maps -------------------------------
  * cm2_cutsky_to_fullsky: d_full is pol arrays of nfull doubles one after the other
  * ([I | Q | U]); component k of observed pixel i, d_map[pol*i + k], goes to
