@@ -23,6 +23,7 @@
 // contiguous compact range [c_w, c_{w+1}), written into / read out of the LDS window beside the valid ones.
 #include "cm2_common.h"
 #include "cm2_perm_window.h"
+#include "cm2_stream.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -33,34 +34,15 @@ using namespace cm2;
 
 namespace {
 
-// the flag of sample i: KIND 0 = int32 pixel ids, flagged when negative; KIND 1 = bytes, flagged when non-zero
-template <int KIND>
-__device__ __forceinline__ bool is_flagged(const void *__restrict__ flags, int64_t i)
-{
-    if (KIND == 0) return static_cast<const int32_t *>(flags)[i] < 0;
-    return static_cast<const uint8_t *>(flags)[i] != 0;
-}
-
+// 1 where sample i is flagged (cm2_stream.h has the two kinds of flags)
 template <int KIND>
 struct FlagAt {
     const void *flags;
     __host__ __device__ __forceinline__ uint32_t operator()(uint32_t i) const
     {
-        if (KIND == 0) return static_cast<const int32_t *>(flags)[i] < 0 ? 1u : 0u;
-        return static_cast<const uint8_t *>(flags)[i] != 0 ? 1u : 0u;
+        return stream::flagged<KIND>(flags, i) ? 1u : 0u;
     }
 };
-
-// block of sample t: the b with off[b] <= t < off[b + 1]
-__host__ __device__ __forceinline__ int64_t block_of(const int64_t *__restrict__ off, int64_t nb, int64_t t)
-{
-    int64_t lo = 0, hi = nb;                       // off[lo] <= t < off[hi]
-    while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (off[mid] <= t) lo = mid; else hi = mid;
-    }
-    return lo;
-}
 
 // 1 where the j-th flagged sample starts a run: the first one, one whose predecessor in time is valid, or the
 // first sample of a block
@@ -73,7 +55,7 @@ struct RunStartAt {
         if (j == 0) return 1u;
         const uint32_t t = pos[j];
         if (pos[j - 1] + 1u != t) return 1u;
-        return off[block_of(off, nb, (int64_t)t)] == (int64_t)t ? 1u : 0u;
+        return off[stream::locate(off, nb, (int64_t)t)] == (int64_t)t ? 1u : 0u;
     }
 };
 
@@ -97,7 +79,7 @@ __global__ __launch_bounds__(256) void k_gap_runs(int64_t nruns, const uint32_t 
     for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < nruns; r += stride) {
         const uint32_t t = pos[j0[r]];
         start[r] = t;
-        blk[r] = (int32_t)block_of(off, nb, (int64_t)t);
+        blk[r] = (int32_t)stream::locate(off, nb, (int64_t)t);
     }
 }
 
@@ -137,7 +119,7 @@ __global__ __launch_bounds__(256) void k_gap_masked_diff(int64_t nt, const void 
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nt; i += stride) {
         const double diff = (n ? n[i] : 0.0) - d[i];
-        u[i] = is_flagged<KIND>(flags, i) ? 0.0 : diff;
+        u[i] = stream::flagged<KIND>(flags, i) ? 0.0 : diff;
     }
 }
 
@@ -148,7 +130,7 @@ __global__ __launch_bounds__(256) void k_gap_copy_valid(int64_t nt, const void *
 {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nt; i += stride)
-        if (!is_flagged<KIND>(flags, i)) out[i] = d[i];
+        if (!stream::flagged<KIND>(flags, i)) out[i] = d[i];
 }
 
 // out at the j-th flagged sample = n there + y_j (n == nullptr: y_j)
@@ -181,9 +163,9 @@ __global__ __launch_bounds__(256) void k_gap_edges(int64_t nruns, const uint32_t
         double sl = 0.0, sr = 0.0;
         int64_t nl = 0, nr = 0;
         for (int64_t i = lo; i < s; ++i)
-            if (!is_flagged<KIND>(flags, i)) { sl += d[i]; ++nl; }
+            if (!stream::flagged<KIND>(flags, i)) { sl += d[i]; ++nl; }
         for (int64_t i = e; i < hi; ++i)
-            if (!is_flagged<KIND>(flags, i)) { sr += d[i]; ++nr; }
+            if (!stream::flagged<KIND>(flags, i)) { sr += d[i]; ++nr; }
         double L = nl ? sl / (double)nl : 0.0, R = nr ? sr / (double)nr : 0.0;
         if (!nl) L = R;
         if (!nr) R = L;
@@ -214,7 +196,7 @@ __global__ __launch_bounds__(256) void k_gap_compare(int64_t nt, const void *__r
 {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     flag_mismatch((int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride, nt, flags, tb_dst, first,
-                  [](const void *__restrict__ f, int64_t i) { return is_flagged<KIND>(f, i); });
+                  [](const void *__restrict__ f, int64_t i) { return stream::flagged<KIND>(f, i); });
 }
 
 // cw[w] = number of flagged samples before window w (lower_bound of w kPermWin in pos), w = 0 .. nwin

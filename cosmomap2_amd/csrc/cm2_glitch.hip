@@ -1,6 +1,7 @@
 // cm2_glitch.hip -- glitch flags from the time streams, see include/cosmomap2.h (f2e): a running median per noise
 // block, the robust scale of its residual by an exact rank selection, the threshold and the grown hits.
-// cm2_glitch_policy.h has the accepted arguments, the tiers, the layout of threads over blocks and the digit split.
+// cm2_glitch_policy.h has the accepted arguments, the tiers, the layout of threads over blocks and the digit split;
+// cm2_stream.h how a kernel sees the stream, its flags and its blocks.
 //
 // Everything here is an order statistic, a comparison or an integer count: no floating-point sum whose order could
 // matter, no floating-point atomic, no cross-lane operation on doubles.  The only arithmetic on doubles is
@@ -30,26 +31,18 @@
 // (cut at the block) in LDS -- the class where the sample alone decides it, a hit mark, or 0 -- and then resolves
 // the 0s to NEAR or CLEAN from the hit marks within grow.  Classes are tallied in LDS and added to counts[b][5] with
 // integer atomics.
-#include <vector>
-
 #include "cm2_common.h"
 #include "cm2_glitch_policy.h"
+#include "cm2_stream.h"
 
 using namespace cm2;
+using namespace cm2::stream;
 namespace gp = cm2::glitch;
 
 namespace {
 
 constexpr uint64_t kAbsMask = 0x7FFFFFFFFFFFFFFFull;
-constexpr uint64_t kExpMask = 0x7FF0000000000000ull;
 constexpr uint8_t kHitMark = 0x80;         // staged byte of a hit (no class has this value)
-
-struct Table {
-    const int64_t *off;                    // [nblocks + 1] first sample of a block
-    const int64_t *run_start;              // [nblocks + 1] first run of a block
-    const int64_t *tile_start;             // [nblocks + 1] first tile of a block
-    int64_t nblocks;
-};
 
 // the selection's state of one block
 struct Pick {
@@ -58,23 +51,7 @@ struct Pick {
     long long m;                           // usable samples of the block
 };
 
-struct Stream {
-    const double *d;
-    const void *flags;                     // NULL: nothing flagged
-    int kind;                              // 0: int32, flagged when negative; 1: bytes, flagged when non-zero
-    const uint8_t *prev;                   // NULL: no earlier pass
-};
-
 __device__ __forceinline__ double pos_inf() { return __longlong_as_double((long long)kExpMask); }
-__device__ __forceinline__ bool finite_bits(double x)
-{
-    return ((unsigned long long)__double_as_longlong(x) & kExpMask) != kExpMask;
-}
-__device__ __forceinline__ bool flagged_at(const Stream &s, int64_t i)
-{
-    if (!s.flags) return false;
-    return s.kind == 0 ? static_cast<const int32_t *>(s.flags)[i] < 0 : static_cast<const uint8_t *>(s.flags)[i] != 0;
-}
 __device__ __forceinline__ bool carried_at(const Stream &s, int64_t i)
 {
     if (!s.prev) return false;
@@ -183,7 +160,7 @@ struct Keys {
 // the residuals go back the same way.  A row is padded to kChunk + 1 doubles: lane L reads its row at a stride of 18
 // banks, which spreads a half-wave over all 64.
 template <int SLOTS, int RS, int THREADS>
-__global__ __launch_bounds__(THREADS) void k_glitch_median(Table t, int h, int64_t runs, Stream s,
+__global__ __launch_bounds__(THREADS) void k_glitch_median(Blocks t, int h, int64_t runs, Stream s,
                                                            double *__restrict__ r)
 {
     constexpr int kChunk = gp::kChunk, kRows = THREADS / kChunk;
@@ -197,7 +174,7 @@ __global__ __launch_bounds__(THREADS) void k_glitch_median(Table t, int h, int64
         gp::Span sp;                               // a thread without a run: an empty span, every key +inf
         int64_t lo = 0, hi = 0;
         if (g < runs) {
-            sp = gp::run_span(t.off, t.run_start, t.nblocks, g);
+            sp = gp::run_span(t.off, t.unit_start, t.nblocks, g);
             lo = t.off[sp.block];
             hi = t.off[sp.block + 1];
         }
@@ -260,13 +237,13 @@ __global__ __launch_bounds__(THREADS) void k_glitch_median(Table t, int h, int64
     }
 }
 
-__global__ __launch_bounds__(gp::kTileThreads) void k_glitch_hist(Table t, int pass, Stream s,
+__global__ __launch_bounds__(gp::kTileThreads) void k_glitch_hist(Blocks t, int pass, Stream s,
                                                                   const double *__restrict__ r,
                                                                   const Pick *__restrict__ state,
                                                                   unsigned int *__restrict__ hist)
 {
     __shared__ unsigned int bins[gp::kMaxBins];
-    const gp::Span sp = gp::tile_span(t.off, t.tile_start, t.nblocks, (int64_t)blockIdx.x);
+    const gp::Span sp = gp::tile_span(t.off, t.unit_start, t.nblocks, (int64_t)blockIdx.x);
     const int nbins = gp::digit_bins(pass), shift = gp::digit_shift(pass);
     for (int j = threadIdx.x; j < nbins; j += gp::kTileThreads) bins[j] = 0u;
     __syncthreads();
@@ -325,14 +302,14 @@ __global__ __launch_bounds__(gp::kTileThreads) void k_glitch_pick(int pass, int 
     for (int k = 0; k < per; ++k) mine[threadIdx.x * per + k] = 0u;
 }
 
-__global__ __launch_bounds__(gp::kTileThreads) void k_glitch_classify(Table t, Stream s, const double *__restrict__ r,
+__global__ __launch_bounds__(gp::kTileThreads) void k_glitch_classify(Blocks t, Stream s, const double *__restrict__ r,
                                                                       const double *__restrict__ sigma, double nsigma,
                                                                       int grow, uint8_t *__restrict__ cls,
                                                                       unsigned long long *__restrict__ counts)
 {
     __shared__ uint8_t stage[gp::kTile + 2 * gp::kMaxGrow];
     __shared__ unsigned int tally[gp::kClasses];
-    const gp::Span sp = gp::tile_span(t.off, t.tile_start, t.nblocks, (int64_t)blockIdx.x);
+    const gp::Span sp = gp::tile_span(t.off, t.unit_start, t.nblocks, (int64_t)blockIdx.x);
     const int64_t lo = t.off[sp.block], hi = t.off[sp.block + 1];
     const double thr = nsigma * sigma[sp.block];
     if (threadIdx.x < gp::kClasses) tally[threadIdx.x] = 0u;
@@ -378,17 +355,18 @@ __global__ __launch_bounds__(kBlock) void k_glitch_apply_pix(int64_t nt, const u
 
 struct cm2_glitch {
     gp::Launch launch;
-    int64_t *d_off = nullptr, *d_run_start = nullptr, *d_tile_start = nullptr;
+    BlockTables tables;                    // the blocks in runs (view 0) and in tiles (view 1)
     unsigned int *d_hist = nullptr;
     Pick *d_state = nullptr;
     int64_t bytes = 0;
-    Table table() const { return Table{d_off, d_run_start, d_tile_start, launch.nblocks}; }
+    Blocks runs() const { return tables.view(0); }
+    Blocks tiles() const { return tables.view(1); }
 };
 
 extern "C" int cm2_glitch_destroy(cm2_glitch *h)
 {
     if (!h) return 0;
-    dev_release(h->d_off, h->d_run_start, h->d_tile_start, h->d_hist, h->d_state);
+    dev_release(h->d_hist, h->d_state);
     delete h;
     return 0;
 }
@@ -398,21 +376,13 @@ namespace {
 int glitch_fill(cm2_glitch *h, const int64_t *sizes, hipStream_t st)
 {
     const size_t nb = (size_t)h->launch.nblocks;
-    std::vector<int64_t> off(nb + 1, 0), runs(nb + 1, 0), tiles(nb + 1, 0);
-    for (size_t b = 0; b < nb; ++b) {
-        off[b + 1] = off[b] + sizes[b];
-        runs[b + 1] = runs[b] + gp::runs_of(sizes[b]);
-        tiles[b + 1] = tiles[b] + gp::tiles_of(sizes[b]);
-    }
-    if (int rc = dev_put(&h->d_off, off.data(), nb + 1, st)) return rc;
-    if (int rc = dev_put(&h->d_run_start, runs.data(), nb + 1, st)) return rc;
-    if (int rc = dev_put(&h->d_tile_start, tiles.data(), nb + 1, st)) return rc;
+    if (int rc = h->tables.fill(sizes, h->launch.nblocks, {gp::kRun, gp::kTile}, st)) return rc;
     CM2_HIP(cm2::dev_malloc(&h->d_hist, (size_t)h->launch.hist_bytes));
     CM2_HIP(cm2::dev_malloc(&h->d_state, sizeof(Pick) * nb));
     CM2_HIP(hipMemsetAsync(h->d_hist, 0, (size_t)h->launch.hist_bytes, st));
     CM2_HIP(hipMemsetAsync(h->d_state, 0, sizeof(Pick) * nb, st));
     CM2_HIP(hipStreamSynchronize(st));
-    h->bytes = (int64_t)(3 * (nb + 1) * sizeof(int64_t) + sizeof(Pick) * nb) + h->launch.hist_bytes;
+    h->bytes = h->tables.bytes() + (int64_t)(sizeof(Pick) * nb) + h->launch.hist_bytes;
     return 0;
 }
 
@@ -422,9 +392,7 @@ int glitch_stream(const char *who, const cm2_glitch *h, const double *d_in, cons
 {
     CM2_CHECK(h, "%s: null handle", who);
     CM2_CHECK(d_in, "%s: null input", who);
-    CM2_CHECK(gp::check_flag_kind(d_flags != nullptr, flag_kind) == gp::kOk,
-              "%s: flag_kind=%d is neither 0 (int32, flagged when negative) nor 1 (bytes, flagged when non-zero)", who,
-              flag_kind);
+    if (int rc = check_flag_kind_status(who, d_flags != nullptr, flag_kind)) return rc;
     *s = Stream{d_in, d_flags, flag_kind, d_prev};
     return 0;
 }
@@ -440,7 +408,7 @@ int launch_median(const cm2_glitch *h, const Stream &s, double *d_r, hipStream_t
         CM2_HIP(ensure_dynamic_lds(reinterpret_cast<const void *>(kernel), (size_t)h->launch.lds_bytes, granted));
     }
     kernel<<<dim3((unsigned)h->launch.median_blocks), kThreads, (size_t)h->launch.lds_bytes, st>>>(
-        h->table(), h->launch.h, h->launch.runs, s, d_r);
+        h->runs(), h->launch.h, h->launch.runs, s, d_r);
     CM2_LAUNCH_OK();
     return 0;
 }
@@ -454,15 +422,8 @@ extern "C" int cm2_glitch_create(cm2_glitch **out, int64_t nt, const int64_t *h_
     CM2_CHECK(out, "%s: null output handle", who);
     gp::Launch l;
     const gp::Status ps = gp::check_create(&l, nt, h_sizes, nblocks, half_width);
-    CM2_CHECK(ps != gp::kBadSize, "%s: nt=%lld and nblocks=%lld must be >= 1 and the sizes given", who, (long long)nt,
-              (long long)nblocks);
-    CM2_CHECK(ps != gp::kBadHalfWidth, "%s: half_width=%d outside [1, %d]", who, half_width, gp::kMaxHalfWidth);
-    CM2_CHECK(ps != gp::kTooLarge, "%s: nt=%lld does not fit the 32-bit sample counts (nt < 2^32 - 1)", who,
-              (long long)nt);
-    CM2_CHECK(ps != gp::kBadBlocks, "%s: the %lld block sizes must be positive and add up to nt=%lld", who,
-              (long long)nblocks, (long long)nt);
-    CM2_CHECK(ps == gp::kOk, "%s: %lld blocks are more than the %lld the histograms allow", who, (long long)nblocks,
-              (long long)gp::kMaxBlocks);
+    if (int rc = check_create_status(who, ps, nt, nblocks, "half_width", half_width, gp::kMaxHalfWidth,
+                                     "the histograms")) return rc;
     cm2_glitch *h = new cm2_glitch();
     h->launch = l;
     const int rc = glitch_fill(h, h_sizes, as_stream(stream));
@@ -517,7 +478,7 @@ extern "C" int cm2_glitch_scale(cm2_glitch *h, const double *d_in, const double 
     hipStream_t st = as_stream(stream);
     CM2_HIP(hipMemsetAsync(h->d_hist, 0, (size_t)h->launch.hist_bytes, st));
     for (int pass = 0; pass < gp::kDigits; ++pass) {
-        k_glitch_hist<<<dim3((unsigned)h->launch.tiles), gp::kTileThreads, 0, st>>>(h->table(), pass, s, d_r,
+        k_glitch_hist<<<dim3((unsigned)h->launch.tiles), gp::kTileThreads, 0, st>>>(h->tiles(), pass, s, d_r,
                                                                                      h->d_state, h->d_hist);
         CM2_LAUNCH_OK();
         k_glitch_pick<<<dim3((unsigned)h->launch.nblocks), gp::kTileThreads, 0, st>>>(
@@ -539,19 +500,18 @@ extern "C" int cm2_glitch_classify(cm2_glitch *h, const double *d_in, const doub
     CM2_CHECK(ps != gp::kBadNsigma, "%s: nsigma=%g must be finite and > 0", who, nsigma);
     CM2_CHECK(ps == gp::kOk, "%s: grow=%d outside [0, %d]", who, grow, gp::kMaxGrow);
     const uint64_t nt = (uint64_t)h->launch.nt, nb = (uint64_t)h->launch.nblocks;
+    const Range cls = {d_class, nt}, counts = {d_counts, 40 * nb}, in = {d_in, 8 * nt}, r = {d_r, 8 * nt},
+                sigma = {d_sigma, 8 * nb};
     // a workgroup reads prev in the halo of its tile, where a neighbour may already have written: never in place
-    CM2_CHECK(!bytes_overlap(d_class, nt, d_prev, nt), "%s: the classes must not overlap prev (the halo of a tile "
-              "reads prev where another workgroup writes)", who);
-    CM2_CHECK(!bytes_overlap(d_class, nt, d_in, 8 * nt) && !bytes_overlap(d_class, nt, d_r, 8 * nt) &&
-              !bytes_overlap(d_class, nt, d_sigma, 8 * nb) && !bytes_overlap(d_class, nt, d_counts, 40 * nb) &&
-              !bytes_overlap(d_class, nt, d_flags, flag_kind == 0 ? 4 * nt : nt),
-              "%s: the classes must not overlap an input or the counts", who);
-    CM2_CHECK(!bytes_overlap(d_counts, 40 * nb, d_in, 8 * nt) && !bytes_overlap(d_counts, 40 * nb, d_r, 8 * nt) &&
-              !bytes_overlap(d_counts, 40 * nb, d_sigma, 8 * nb), "%s: the counts must not overlap an input", who);
+    if (int rc = check_disjoint(who, {cls}, {{d_prev, nt}}, "%s: the classes must not overlap prev (the halo of a tile "
+                                "reads prev where another workgroup writes)")) return rc;
+    if (int rc = check_disjoint(who, {cls}, {in, r, sigma, counts, {d_flags, flag_kind == 0 ? 4 * nt : nt}},
+                                "%s: the classes must not overlap an input or the counts")) return rc;
+    if (int rc = check_disjoint(who, {counts}, {in, r, sigma}, "%s: the counts must not overlap an input")) return rc;
     hipStream_t st = as_stream(stream);
     CM2_HIP(hipMemsetAsync(d_counts, 0, (size_t)(40 * nb), st));
     k_glitch_classify<<<dim3((unsigned)h->launch.tiles), gp::kTileThreads, 0, st>>>(
-        h->table(), s, d_r, d_sigma, nsigma, grow, d_class, reinterpret_cast<unsigned long long *>(d_counts));
+        h->tiles(), s, d_r, d_sigma, nsigma, grow, d_class, reinterpret_cast<unsigned long long *>(d_counts));
     CM2_LAUNCH_OK();
     return 0;
 }

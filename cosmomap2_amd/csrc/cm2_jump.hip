@@ -1,7 +1,8 @@
 // cm2_jump.hip -- baseline jumps of the time streams, see include/cosmomap2.h (f2f): the step statistic t of every
 // position from two window means, its robust scale (the selection of cm2_glitch), the jumps as the local maxima of |t|
 // beyond the threshold, their accumulated offsets, and the corrected stream with its classes.
-// cm2_jump_policy.h has the accepted arguments, the tiles and what a tile of the statistic kernel holds in LDS.
+// cm2_jump_policy.h has the accepted arguments, the tiles and what a tile of the statistic kernel holds in LDS;
+// cm2_stream.h how a kernel sees the stream, its flags and its blocks.
 //
 // The floating-point operations are the ones of the definition, each rounded on its own (the unit is compiled with
 // -ffp-contract=off): the w additions of a window sum in ascending sample order from +0.0, two divisions and one
@@ -28,50 +29,27 @@
 // sample then bisects that short range (empty for nearly every tile) for m(i): the entry before gives the offset and
 // whether the sample is a jump, the entries on either side whether one lies within radius.
 #include <iterator>
-#include <vector>
 
 #include <hipcub/hipcub.hpp>
 
 #include "cm2_common.h"
 #include "cm2_jump_policy.h"
+#include "cm2_stream.h"
 
 using namespace cm2;
+using namespace cm2::stream;
 namespace jp = cm2::jump;
 
 namespace {
-
-constexpr uint64_t kExpMask = 0x7FF0000000000000ull;
-
-struct Table {
-    const int64_t *off;                    // [nblocks + 1] first sample of a block
-    const int64_t *tile_start;             // [nblocks + 1] first tile of a block
-    int64_t nblocks;
-};
-
-struct Stream {
-    const double *d;
-    const void *flags;                     // NULL: nothing flagged
-    int kind;                              // 0: int32, flagged when negative; 1: bytes, flagged when non-zero
-    const uint8_t *prev;                   // NULL: no earlier classes
-};
-
-__device__ __forceinline__ bool finite_bits(double x)
-{
-    return ((unsigned long long)__double_as_longlong(x) & kExpMask) != kExpMask;
-}
 
 // rule 1; *x = d_i
 __device__ __forceinline__ bool usable_at(const Stream &s, int64_t i, double *x)
 {
     *x = s.d[i];
-    bool flagged = false;
-    if (s.flags)
-        flagged = s.kind == 0 ? static_cast<const int32_t *>(s.flags)[i] < 0
-                              : static_cast<const uint8_t *>(s.flags)[i] != 0;
-    return !flagged && finite_bits(*x) && !(s.prev && s.prev[i] != 0);
+    return !flagged_at(s, i) && finite_bits(*x) && !(s.prev && s.prev[i] != 0);
 }
 
-__global__ __launch_bounds__(jp::kTileThreads) void k_jump_stat(Table tb, int w, int min_count, Stream s,
+__global__ __launch_bounds__(jp::kTileThreads) void k_jump_stat(Blocks tb, int w, int min_count, Stream s,
                                                                  double *__restrict__ t, uint8_t *__restrict__ noeval)
 {
     extern __shared__ double lds[];
@@ -79,7 +57,7 @@ __global__ __launch_bounds__(jp::kTileThreads) void k_jump_stat(Table tb, int w,
     const int nvals = jp::stat_values(w), tid = threadIdx.x;
     double *vals = lds, *S = lds + nvals;
     uint16_t *C = reinterpret_cast<uint16_t *>(S + jp::stat_starts());        // C[v] = usable among vals[0, v)
-    const jp::Span sp = jp::tile_span(tb.off, tb.tile_start, tb.nblocks, (int64_t)blockIdx.x);
+    const jp::Span sp = jp::tile_span(tb.off, tb.unit_start, tb.nblocks, (int64_t)blockIdx.x);
     const int64_t lo = tb.off[sp.block], hi = tb.off[sp.block + 1];
     const int len = (int)(sp.end - sp.first);
     const int64_t base = sp.first - w;                                        // the sample of vals[0]
@@ -148,7 +126,7 @@ __global__ __launch_bounds__(jp::kTileThreads) void k_jump_stat(Table tb, int w,
     }
 }
 
-__global__ __launch_bounds__(jp::kTileThreads) void k_jump_peaks(Table tb, int w, const double *__restrict__ t,
+__global__ __launch_bounds__(jp::kTileThreads) void k_jump_peaks(Blocks tb, int w, const double *__restrict__ t,
                                                                   const uint8_t *__restrict__ noeval,
                                                                   const double *__restrict__ sigma, double nsigma,
                                                                   uint8_t *__restrict__ mark,
@@ -156,7 +134,7 @@ __global__ __launch_bounds__(jp::kTileThreads) void k_jump_peaks(Table tb, int w
 {
     __shared__ double a[jp::kTile + 2 * jp::kMaxWindow];
     __shared__ unsigned int tally;
-    const jp::Span sp = jp::tile_span(tb.off, tb.tile_start, tb.nblocks, (int64_t)blockIdx.x);
+    const jp::Span sp = jp::tile_span(tb.off, tb.unit_start, tb.nblocks, (int64_t)blockIdx.x);
     const int64_t lo = tb.off[sp.block], hi = tb.off[sp.block + 1];
     const int len = (int)(sp.end - sp.first);
     const int64_t base = sp.first - w;
@@ -205,7 +183,7 @@ __global__ __launch_bounds__(kBlock) void k_jump_offsets(const int64_t *__restri
     }
 }
 
-__global__ __launch_bounds__(jp::kTileThreads) void k_jump_correct(Table tb, const double *d_in,
+__global__ __launch_bounds__(jp::kTileThreads) void k_jump_correct(Blocks tb, const double *d_in,
                                                                     const uint8_t *__restrict__ prev,
                                                                     const int64_t *__restrict__ pos,
                                                                     const double *__restrict__ offsets,
@@ -216,7 +194,7 @@ __global__ __launch_bounds__(jp::kTileThreads) void k_jump_correct(Table tb, con
 {
     __shared__ int64_t range[2];
     __shared__ unsigned int tally[jp::kCounts];
-    const jp::Span sp = jp::tile_span(tb.off, tb.tile_start, tb.nblocks, (int64_t)blockIdx.x);
+    const jp::Span sp = jp::tile_span(tb.off, tb.unit_start, tb.nblocks, (int64_t)blockIdx.x);
     const int64_t lo = tb.off[sp.block], hi = tb.off[sp.block + 1], n = table_size(total, capacity);
     if (threadIdx.x < jp::kCounts) tally[threadIdx.x] = 0u;
     if (threadIdx.x == 0) {
@@ -284,20 +262,20 @@ hipError_t select_marked(void *d_temp, size_t *temp_bytes, const uint8_t *d_mark
 
 struct cm2_jump {
     jp::Launch launch;
-    int64_t *d_off = nullptr, *d_tile_start = nullptr;
+    BlockTables tables;                    // the blocks in tiles
     uint8_t *d_mark = nullptr;             // [nt] the jumps of the last cm2_jump_find
     char *d_temp = nullptr;                // the select's
     size_t temp_bytes = 0;
     cm2_glitch *scale = nullptr;           // half-width 1: its selection gives the scale of t
     int64_t bytes = 0;
-    Table table() const { return Table{d_off, d_tile_start, launch.nblocks}; }
+    Blocks tiles() const { return tables.view(0); }
 };
 
 extern "C" int cm2_jump_destroy(cm2_jump *h)
 {
     if (!h) return 0;
     cm2_glitch_destroy(h->scale);
-    dev_release(h->d_off, h->d_tile_start, h->d_mark, h->d_temp);
+    dev_release(h->d_mark, h->d_temp);
     delete h;
     return 0;
 }
@@ -307,21 +285,15 @@ namespace {
 int jump_fill(cm2_jump *h, const int64_t *sizes, void *stream)
 {
     hipStream_t st = as_stream(stream);
-    const size_t nb = (size_t)h->launch.nblocks, nt = (size_t)h->launch.nt;
-    std::vector<int64_t> off(nb + 1, 0), tiles(nb + 1, 0);
-    for (size_t b = 0; b < nb; ++b) {
-        off[b + 1] = off[b] + sizes[b];
-        tiles[b + 1] = tiles[b] + jp::tiles_of(sizes[b]);
-    }
-    if (int rc = dev_put(&h->d_off, off.data(), nb + 1, st)) return rc;
-    if (int rc = dev_put(&h->d_tile_start, tiles.data(), nb + 1, st)) return rc;
+    const size_t nt = (size_t)h->launch.nt;
+    if (int rc = h->tables.fill(sizes, h->launch.nblocks, {jp::kTile}, st)) return rc;
     CM2_HIP(cm2::dev_malloc(&h->d_mark, nt));
     CM2_HIP(select_marked(nullptr, &h->temp_bytes, h->d_mark, h->launch.nt, nullptr, 1, nullptr, st));
     CM2_HIP(cm2::dev_malloc(&h->d_temp, h->temp_bytes + 16));
     if (int rc = cm2_glitch_create(&h->scale, h->launch.nt, sizes, h->launch.nblocks, 1, stream)) return rc;
     int64_t ginfo[6];
     if (int rc = cm2_glitch_info(h->scale, ginfo)) return rc;
-    h->bytes = (int64_t)(2 * (nb + 1) * sizeof(int64_t) + nt + h->temp_bytes + 16) + ginfo[5];
+    h->bytes = h->tables.bytes() + (int64_t)(nt + h->temp_bytes + 16) + ginfo[5];
     return 0;
 }
 
@@ -334,15 +306,8 @@ extern "C" int cm2_jump_create(cm2_jump **out, int64_t nt, const int64_t *h_size
     CM2_CHECK(out, "%s: null output handle", who);
     jp::Launch l;
     const jp::Status ps = jp::check_create(&l, nt, h_sizes, nblocks, half_window);
-    CM2_CHECK(ps != jp::kBadSize, "%s: nt=%lld and nblocks=%lld must be >= 1 and the sizes given", who, (long long)nt,
-              (long long)nblocks);
-    CM2_CHECK(ps != jp::kBadWindow, "%s: half_window=%d outside [1, %d]", who, half_window, jp::kMaxWindow);
-    CM2_CHECK(ps != jp::kTooLarge, "%s: nt=%lld does not fit the 32-bit sample counts (nt < 2^32 - 1)", who,
-              (long long)nt);
-    CM2_CHECK(ps != jp::kBadBlocks, "%s: the %lld block sizes must be positive and add up to nt=%lld", who,
-              (long long)nblocks, (long long)nt);
-    CM2_CHECK(ps == jp::kOk, "%s: %lld blocks are more than the %lld the scale's histograms allow", who,
-              (long long)nblocks, (long long)jp::kMaxBlocks);
+    if (int rc = check_create_status(who, ps, nt, nblocks, "half_window", half_window, jp::kMaxWindow,
+                                     "the scale's histograms")) return rc;
     cm2_jump *h = new cm2_jump();
     h->launch = l;
     const int rc = jump_fill(h, h_sizes, stream);
@@ -372,21 +337,19 @@ extern "C" int cm2_jump_stat(cm2_jump *h, const double *d_in, const void *d_flag
     const char *who = "cm2_jump_stat";
     CM2_CHECK(h, "%s: null handle", who);
     CM2_CHECK(d_in && d_t && d_noeval, "%s: null input or output", who);
-    const jp::Status ps = jp::check_stat(h->launch.w, d_flags != nullptr, flag_kind, min_count);
-    CM2_CHECK(ps != jp::kBadFlagKind,
-              "%s: flag_kind=%d is neither 0 (int32, flagged when negative) nor 1 (bytes, flagged when non-zero)", who,
-              flag_kind);
-    CM2_CHECK(ps == jp::kOk, "%s: min_count=%d outside [1, half_window=%d]", who, min_count, h->launch.w);
-    const uint64_t nt = (uint64_t)h->launch.nt, nf = flag_kind == 0 ? 4 * nt : nt;
-    CM2_CHECK(!bytes_overlap(d_t, 8 * nt, d_in, 8 * nt) && !bytes_overlap(d_t, 8 * nt, d_flags, nf) &&
-              !bytes_overlap(d_t, 8 * nt, d_prev, nt) && !bytes_overlap(d_t, 8 * nt, d_noeval, nt),
-              "%s: t must not overlap an input or noeval", who);
-    CM2_CHECK(!bytes_overlap(d_noeval, nt, d_in, 8 * nt) && !bytes_overlap(d_noeval, nt, d_flags, nf) &&
-              !bytes_overlap(d_noeval, nt, d_prev, nt), "%s: noeval must not overlap an input", who);
+    if (int rc = check_flag_kind_status(who, d_flags != nullptr, flag_kind)) return rc;
+    CM2_CHECK(jp::check_stat(h->launch.w, d_flags != nullptr, flag_kind, min_count) == jp::kOk,
+              "%s: min_count=%d outside [1, half_window=%d]", who, min_count, h->launch.w);
+    const uint64_t nt = (uint64_t)h->launch.nt;
+    const Range in = {d_in, 8 * nt}, flags = {d_flags, flag_kind == 0 ? 4 * nt : nt}, prev = {d_prev, nt},
+                noeval = {d_noeval, nt};
+    if (int rc = check_disjoint(who, {{d_t, 8 * nt}}, {in, flags, prev, noeval},
+                                "%s: t must not overlap an input or noeval")) return rc;
+    if (int rc = check_disjoint(who, {noeval}, {in, flags, prev}, "%s: noeval must not overlap an input")) return rc;
     static size_t granted[64] = {0};
     CM2_HIP(ensure_dynamic_lds(reinterpret_cast<const void *>(k_jump_stat), (size_t)h->launch.lds_bytes, granted));
     k_jump_stat<<<dim3((unsigned)h->launch.tiles), jp::kTileThreads, (size_t)h->launch.lds_bytes, as_stream(stream)>>>(
-        h->table(), h->launch.w, min_count, Stream{d_in, d_flags, flag_kind, d_prev}, d_t, d_noeval);
+        h->tiles(), h->launch.w, min_count, Stream{d_in, d_flags, flag_kind, d_prev}, d_t, d_noeval);
     CM2_LAUNCH_OK();
     return 0;
 }
@@ -416,25 +379,19 @@ extern "C" int cm2_jump_find(cm2_jump *h, const double *d_t, const uint8_t *d_no
     CM2_CHECK(ps == jp::kOk, "%s: capacity=%lld < 1", who, (long long)capacity);
     const uint64_t nt = (uint64_t)h->launch.nt, nb = (uint64_t)h->launch.nblocks;
     const uint64_t cap = 8 * (uint64_t)(capacity < h->launch.nt ? capacity : h->launch.nt);   // bytes a table can take
-    const void *outs[4] = {d_pos, d_heights, d_offsets, d_njumps};
-    const uint64_t out_bytes[4] = {cap, cap, cap, 8 * (nb + 1)};
-    for (int a = 0; a < 4; ++a) {
-        CM2_CHECK(!bytes_overlap(outs[a], out_bytes[a], d_t, 8 * nt) &&
-                  !bytes_overlap(outs[a], out_bytes[a], d_noeval, nt) &&
-                  !bytes_overlap(outs[a], out_bytes[a], d_sigma, 8 * nb), "%s: an output overlaps an input", who);
-        for (int b = a + 1; b < 4; ++b)
-            CM2_CHECK(!bytes_overlap(outs[a], out_bytes[a], outs[b], out_bytes[b]), "%s: two outputs overlap", who);
-    }
+    if (int rc = check_disjoint(who, {{d_pos, cap}, {d_heights, cap}, {d_offsets, cap}, {d_njumps, 8 * (nb + 1)}},
+                                {{d_t, 8 * nt}, {d_noeval, nt}, {d_sigma, 8 * nb}}, "%s: an output overlaps an input",
+                                "%s: two outputs overlap")) return rc;
     hipStream_t st = as_stream(stream);
     CM2_HIP(hipMemsetAsync(d_njumps, 0, (size_t)(8 * (nb + 1)), st));
     k_jump_peaks<<<dim3((unsigned)h->launch.tiles), jp::kTileThreads, 0, st>>>(
-        h->table(), h->launch.w, d_t, d_noeval, d_sigma, nsigma, h->d_mark,
+        h->tiles(), h->launch.w, d_t, d_noeval, d_sigma, nsigma, h->d_mark,
         reinterpret_cast<unsigned long long *>(d_njumps));
     CM2_LAUNCH_OK();
     size_t temp_bytes = h->temp_bytes;
     CM2_HIP(select_marked(h->d_temp, &temp_bytes, h->d_mark, h->launch.nt, d_pos, capacity, d_njumps + nb, st));
     k_jump_offsets<<<dim3((unsigned)((nb + kBlock - 1) / kBlock)), kBlock, 0, st>>>(
-        h->d_off, h->launch.nblocks, d_pos, d_njumps + nb, capacity, d_t, d_heights, d_offsets);
+        h->tables.d_off, h->launch.nblocks, d_pos, d_njumps + nb, capacity, d_t, d_heights, d_offsets);
     CM2_LAUNCH_OK();
     return 0;
 }
@@ -451,21 +408,16 @@ extern "C" int cm2_jump_correct(cm2_jump *h, const double *d_in, const uint8_t *
     CM2_CHECK(ps == jp::kOk, "%s: capacity=%lld < 1", who, (long long)capacity);
     const uint64_t nt = (uint64_t)h->launch.nt, nb = (uint64_t)h->launch.nblocks;
     const uint64_t cap = 8 * (uint64_t)(capacity < h->launch.nt ? capacity : h->launch.nt);
-    const void *ins[5] = {d_in, d_prev, d_pos, d_offsets, d_njumps};
-    const uint64_t in_bytes[5] = {8 * nt, nt, cap, cap, 8 * (nb + 1)};
-    const void *outs[3] = {d_out, d_class, d_counts};
-    const uint64_t out_bytes[3] = {8 * nt, nt, 8 * jp::kCounts * nb};
-    for (int a = 0; a < 3; ++a) {
-        for (int b = 0; b < 5; ++b)                                   // (a sample is read and written by one thread)
-            CM2_CHECK((a == 0 && b == 0 && d_out == d_in) || !bytes_overlap(outs[a], out_bytes[a], ins[b], in_bytes[b]),
-                      "%s: an output overlaps an input (only d_out may be d_in itself)", who);
-        for (int b = a + 1; b < 3; ++b)
-            CM2_CHECK(!bytes_overlap(outs[a], out_bytes[a], outs[b], out_bytes[b]), "%s: two outputs overlap", who);
-    }
+    // d_out may be d_in itself: a sample is read and written by one thread
+    const Range table = {d_pos, cap}, offsets = {d_offsets, cap}, njumps = {d_njumps, 8 * (nb + 1)};
+    if (int rc = check_disjoint(who, {{d_out, 8 * nt}, {d_class, nt}, {d_counts, 8 * jp::kCounts * nb}},
+                                {{d_in, 8 * nt}, {d_prev, nt}, table, offsets, njumps},
+                                "%s: an output overlaps an input (only d_out may be d_in itself)",
+                                "%s: two outputs overlap", 0, 0)) return rc;
     hipStream_t st = as_stream(stream);
     CM2_HIP(hipMemsetAsync(d_counts, 0, (size_t)(8 * jp::kCounts * nb), st));
     k_jump_correct<<<dim3((unsigned)h->launch.tiles), jp::kTileThreads, 0, st>>>(
-        h->table(), d_in, d_prev, d_pos, d_offsets, d_njumps + nb, capacity, radius, d_out, d_class,
+        h->tiles(), d_in, d_prev, d_pos, d_offsets, d_njumps + nb, capacity, radius, d_out, d_class,
         reinterpret_cast<unsigned long long *>(d_counts));
     CM2_LAUNCH_OK();
     return 0;

@@ -2,10 +2,8 @@
 // how workgroups are laid over the noise blocks, and what one tile of the statistic kernel holds in LDS.  Plain C++:
 // tests/test_jump_cpu.py compiles it with the host compiler and checks it against Python.
 //
-// The stream is nblocks noise blocks one after the other, block b the samples [off[b], off[b + 1]).  A *tile* is kTile
-// consecutive samples of one block (the last tile of a block may be shorter), the tiles of the stream are numbered
-// block after block, tile_start[b] the first of block b, and workgroup g takes tile g: the tiles, their prefix table
-// and its bisection are the ones of cm2_glitch_policy.h.  One workgroup therefore sees one block only.
+// cm2_stream_policy.h has the blocks, their tiles of kTile samples and the checks every stage shares; its names are
+// reachable as cm2::jump:: too.  Workgroup g takes tile g in every kernel, so one workgroup sees one block only.
 //
 // Statistic.  The t of the positions [first, end) of a tile needs the window sums S_j of the starts j = first - w ..
 // end - 1 (R_i = S_i, L_i = S_{i-w}), and those the samples first - w .. end + w - 2.  A workgroup stages
@@ -14,40 +12,26 @@
 #pragma once
 #include <cstdint>
 
-#include "cm2_glitch_policy.h"
+#include "cm2_stream_policy.h"
 
 namespace cm2 {
 namespace jump {
 
-using glitch::Span;
-using glitch::locate;
-using glitch::tile_span;
-using glitch::tiles_of;
+using namespace stream;
 
 constexpr int kMaxWindow = 256;            // 1 <= w <= 256, the half-window: w samples on either side of a position
 constexpr int kMaxRadius = 256;
-constexpr int kTile = glitch::kTile;       // positions of one workgroup, every kernel
 constexpr int kTileThreads = 256;
 constexpr int kCounts = 3;                 // counts[b][CLEAN, AT, NEAR]
-constexpr int64_t kMaxBlocks = glitch::kMaxBlocks;
 constexpr int64_t kLdsLimit = 64 * 1024;   // of one workgroup
 
 // the classes a pass adds (CM2_JUMP_* of include/cosmomap2.h)
 enum Class { kClean = 0, kAt = 1, kNear = 2 };
 
-enum Status {
-    kOk = 0,
-    kBadSize = 1,          // nt < 1, nblocks < 1 or no sizes
-    kBadBlocks = 2,        // a size < 1, or the sizes do not add up to nt
-    kBadWindow = 3,        // w outside [1, 256]
-    kTooLarge = 4,         // nt >= 2^32 - 1
-    kTooManyBlocks = 5,    // nblocks > kMaxBlocks
-    kBadNsigma = 6,        // not finite or <= 0
-    kBadRadius = 7,        // outside [0, 256]
-    kBadFlagKind = 8,      // flags given with a kind other than 0 or 1
-    kBadMinCount = 9,      // outside [1, w]
-    kBadCapacity = 10      // < 1
-};
+// the codes of this stage beside the shared ones (kBadWindow: w outside [1, 256])
+constexpr Status kBadRadius = Status(7);           // outside [0, 256]
+constexpr Status kBadMinCount = Status(9);         // outside [1, w]
+constexpr Status kBadCapacity = Status(10);        // < 1
 
 // ---- one tile of the statistic kernel -----------------------------------------------------------------------------
 // window starts a thread sums, all at once (independent chains of additions): ceil((kTile + kMaxWindow) / threads)
@@ -73,24 +57,14 @@ struct Launch {
     int64_t lds_bytes = 0;
 };
 
-// fills *l; anything but kOk leaves it unspecified.  nt < 2^32 - 1 keeps the tile count (a grid dimension) below 2^31.
+// fills *l; anything but kOk leaves it unspecified
 inline Status check_create(Launch *l, int64_t nt, const int64_t *sizes, int64_t nblocks, int half_window)
 {
-    if (nt < 1 || nblocks < 1 || !sizes) return kBadSize;
-    if (half_window < 1 || half_window > kMaxWindow) return kBadWindow;
-    if (nt >= (((int64_t)1 << 32) - 1)) return kTooLarge;
-    if (nblocks > nt) return kBadBlocks;
-    int64_t sum = 0, tiles = 0;
-    for (int64_t b = 0; b < nblocks; ++b) {
-        if (sizes[b] < 1 || sizes[b] > nt - sum) return kBadBlocks;
-        sum += sizes[b];
-        tiles += tiles_of(sizes[b]);
-    }
-    if (sum != nt) return kBadBlocks;
-    if (nblocks > kMaxBlocks) return kTooManyBlocks;
+    const Status st = check_blocks(nt, sizes, nblocks, half_window >= 1 && half_window <= kMaxWindow);
+    if (st != kOk) return st;
     l->nt = nt;
     l->nblocks = nblocks;
-    l->tiles = tiles;
+    l->tiles = total_units(sizes, nblocks, kTile);
     l->w = half_window;
     l->lds_bytes = stat_lds_bytes(half_window);
     return kOk;
@@ -98,14 +72,14 @@ inline Status check_create(Launch *l, int64_t nt, const int64_t *sizes, int64_t 
 
 inline Status check_stat(int w, bool have_flags, int kind, int min_count)
 {
-    if (have_flags && kind != 0 && kind != 1) return kBadFlagKind;
+    if (check_flag_kind(have_flags, kind) != kOk) return kBadFlagKind;
     if (min_count < 1 || min_count > w) return kBadMinCount;
     return kOk;
 }
 
 inline Status check_find(double nsigma, int64_t capacity)
 {
-    if (!(nsigma > 0.0) || !(nsigma <= 1.7976931348623157e308)) return kBadNsigma;
+    if (check_nsigma(nsigma) != kOk) return kBadNsigma;
     if (capacity < 1) return kBadCapacity;
     return kOk;
 }

@@ -21,6 +21,7 @@
 // whichever segments share its batch, and the per-bin sums run in segment order across batch boundaries:
 // a block estimated alone gives the bits of the same block estimated inside a group.
 #include "cm2_rocfft.h"
+#include "cm2_stream_policy.h"
 
 #include <cmath>
 #include <vector>
@@ -33,17 +34,6 @@ constexpr int64_t kMinL = 256, kMaxL = 65536;
 constexpr int64_t kBatchSamples = int64_t(1) << 24;     // segments per batch * L, at most (128 MB of input)
 
 bool pow2_in_range(int64_t L) { return L >= kMinL && L <= kMaxL && (L & (L - 1)) == 0; }
-
-// largest b with off[b] <= k (off ascending, off[0] = 0 <= k)
-__device__ __forceinline__ int64_t upper_block(const int64_t *__restrict__ off, int64_t nb, int64_t k)
-{
-    int64_t lo = 0, hi = nb;
-    while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (off[mid] <= k) lo = mid; else hi = mid;
-    }
-    return lo;
-}
 
 // One workgroup per segment of the batch: gather the L samples of segment g = first + blockIdx.x, subtract
 // their mean (detrend = 1: every thread sums its samples j = t, t+256, ... in order, then the fixed tree of
@@ -60,7 +50,7 @@ __global__ __launch_bounds__(256) void k_psd_pack(const double *__restrict__ tod
         for (int64_t j = threadIdx.x; j < L; j += blockDim.x) x[j] = 0.0;
         return;
     }
-    const int64_t b = upper_block(seg_off, nb, g);
+    const int64_t b = stream::locate(seg_off, nb, g);       // segments are numbered block after block
     const double *src = tod + off[b] + (g - seg_off[b]) * (L / 2);
     double mean = 0.0;
     if (detrend) {

@@ -13,6 +13,8 @@
 #pragma once
 #include <cstdint>
 
+#include "cm2_stream_policy.h"
+
 #if defined(__HIPCC__)
 #define CM2_OFF_HD __host__ __device__ __forceinline__
 #else
@@ -34,18 +36,10 @@ CM2_OFF_HD int pad(int q) { return q + (q >> 5); }
 CM2_OFF_HD int64_t baselines_in(int64_t n, int64_t L) { return (n + L - 1) / L; }
 
 // block of sample t: the b with off[b] <= t < off[b + 1]
-CM2_OFF_HD int64_t block_of(const int64_t *off, int64_t nb, int64_t t)
-{
-    int64_t lo = 0, hi = nb;
-    while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (off[mid] <= t) lo = mid; else hi = mid;
-    }
-    return lo;
-}
+CM2_OFF_HD int64_t block_of(const int64_t *off, int64_t nb, int64_t t) { return stream::locate(off, nb, t); }
 
 // block of baseline j: the b with j0[b] <= j < j0[b + 1]
-CM2_OFF_HD int64_t block_of_baseline(const int64_t *j0, int64_t nb, int64_t j) { return block_of(j0, nb, j); }
+CM2_OFF_HD int64_t block_of_baseline(const int64_t *j0, int64_t nb, int64_t j) { return stream::locate(j0, nb, j); }
 
 struct Baseline {
     int64_t j;              // global index

@@ -46,10 +46,8 @@ import numpy as np
 from .. import _hip
 from .. import device as D
 from .. import linop as lp
-from ..utilities.gap_fill import _check_tod
-from ..utilities.noise_model import _block_sizes, _int
+from ..utilities._stream_args import _block_sizes, _check_rtol, _check_tod, _int
 from . import linearoperators as L
-from .gapaware import _check_rtol
 
 __all__ = ["OffsetsLO", "DestriperNormalLO", "solve_destriped"]
 

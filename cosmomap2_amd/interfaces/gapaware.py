@@ -34,8 +34,8 @@ import numpy as np
 from .. import _hip
 from .. import device as D
 from .. import linop as lp
-from ..utilities.gap_fill import _Gaps, _check_tod
-from ..utilities.noise_model import _int
+from ..utilities._stream_args import _check_rtol, _check_tod, _int
+from ..utilities.gap_fill import _Gaps
 from . import linearoperators as L
 
 __all__ = ["GapAwareNormalLO", "solve_gls_with_gaps"]
@@ -55,16 +55,6 @@ def _check_operators(P, N):
     if not all(np.isfinite(a) and a > 0 for a in a0):
         raise ValueError("every block's band must start with a positive a_0, got %r" % (a0,))
     return sizes, nt, a0
-
-
-def _check_rtol(rtol):
-    try:
-        rtol = float(rtol)
-    except (TypeError, ValueError):
-        raise ValueError("rtol must be a positive number, got %r" % (rtol,))
-    if not (np.isfinite(rtol) and rtol > 0):
-        raise ValueError("rtol must be a positive number, got %r" % (rtol,))
-    return rtol
 
 
 class GapAwareNormalLO(L._DeviceOp):

@@ -49,74 +49,10 @@ import numpy as np
 
 from .. import _hip
 from .. import device as D
-from .noise_model import _block_sizes, _int, _tod_length
-from .noise_sim import NoiseSimulator, _u64
+from ._stream_args import _block_sizes, _check_flags, _check_out, _check_tod, _flags_to_dev, _int, _u64
+from .noise_sim import NoiseSimulator
 
 __all__ = ["GapFiller", "fill_gaps_linear"]
-
-_MAX_NT = (1 << 32) - 2
-
-
-def _check_flags(flags, nt=None):
-    """Length of a 1-D flag array (integer or bool, NumPy or tensor), without touching the GPU."""
-    if D.is_tensor(flags):
-        t = D.torch
-        if flags.dtype not in (t.int32, t.bool, t.uint8):
-            raise ValueError("a flags tensor must be int32 (flagged where negative) or bool, got %s" % flags.dtype)
-        shape = tuple(flags.shape)
-    else:
-        a = np.asarray(flags)
-        if not (a.dtype == np.bool_ or np.issubdtype(a.dtype, np.signedinteger)):
-            raise ValueError("flags must be signed integers (flagged where negative) or bool, got dtype %s" % a.dtype)
-        shape = a.shape
-    if len(shape) != 1 or shape[0] < 1:
-        raise ValueError("flags must be a one-dimensional array with at least one sample, got shape %s" % (shape,))
-    n = int(shape[0])
-    if n > _MAX_NT:
-        raise ValueError("%d samples do not fit the 32-bit sample index of the gap table" % n)
-    if nt is not None and n != nt:
-        raise ValueError("%d flags for %d samples" % (n, nt))
-    return n
-
-
-def _flags_to_dev(flags):
-    """(contiguous device tensor, kind) with kind 0 = int32 pixel ids, 1 = bytes."""
-    t = D.torch
-    if D.is_tensor(flags):
-        if flags.dtype == t.int32:
-            return D.to_dev(flags), 0
-        return D.to_dev(flags).view(t.uint8), 1
-    a = np.asarray(flags)
-    if a.dtype == np.int32:
-        return D.to_dev(a), 0
-    if a.dtype != np.bool_:
-        a = a < 0
-    return D.to_dev(np.ascontiguousarray(a).view(np.uint8)), 1
-
-
-def _check_tod(name, d, nt):
-    if _tod_length(d) != nt:
-        raise ValueError("%s has %d samples, the flags %d" % (name, _tod_length(d), nt))
-    if D.is_tensor(d) and not d.is_cuda:
-        raise ValueError("a %s tensor must be in HBM, got device %s" % (name, d.device))
-
-
-def _check_out(out, nt):
-    """``out`` as NoiseSimulator.draw takes it: None, a float64 tensor in HBM or a NumPy array of nt samples."""
-    if out is None:
-        return
-    if D.is_tensor(out):
-        if not out.is_cuda or out.dtype != D.torch.float64:
-            raise ValueError("an out tensor must be float64 in HBM, got %s on %s" % (out.dtype, out.device))
-        if out.dim() != 1 or out.numel() != nt or not out.is_contiguous():
-            raise ValueError("out must be a contiguous vector of %d samples, got shape %s" % (nt, tuple(out.shape)))
-    elif isinstance(out, np.ndarray):
-        if out.dtype != np.float64:
-            raise ValueError("an out array must be float64, got %s" % out.dtype)
-        if out.ndim != 1 or out.size != nt or not out.flags.c_contiguous or not out.flags.writeable:
-            raise ValueError("out must be a writeable contiguous vector of %d samples, got shape %s" % (nt, out.shape))
-    else:
-        raise ValueError("out must be a float64 tensor in HBM or a NumPy array, got %r" % type(out))
 
 
 def _check_nedge(nedge):

@@ -28,14 +28,14 @@ Every result is an order statistic or a count: the same bits on every run.  Ever
 is touched (``ValueError``); without a GPU a valid call raises ``HipError``.  On several GPUs each rank flags its own
 blocks (``sharding.shard_blocks``): blocks are independent, so this is the same result.
 """
-import ctypes
-
 import numpy as np
 
 from .. import _hip
 from .. import device as D
-from .gap_fill import _check_flags, _check_tod, _flags_to_dev
-from .noise_model import _block_sizes, _int, _tod_length
+from ._stream_args import MAX_ITERATIONS                     # noqa: F401  (a limit of flag(), public here)
+from ._stream_args import _flags_to_dev                      # noqa: F401  (tests/test_gpu_glitch.py looks it up here)
+from ._stream_args import (_MAX_NT, _BlockStage, _StageHandle, _check_classes, _check_iterations, _check_nsigma,
+                           _check_sigma, _int, _tod_length)
 
 __all__ = ["GlitchFlagger", "flag_glitches", "apply_flags", "GLITCH_CLASSES"]
 
@@ -43,9 +43,6 @@ GLITCH_CLASSES = ("clean", "input", "nonfinite", "hit", "near")
 CLEAN, INPUT, NONFINITE, HIT, NEAR = range(5)
 MAX_HALF_WIDTH = 64            # CM2_GLITCH_MAX_HALF_WIDTH
 MAX_GROW = 64                  # CM2_GLITCH_MAX_GROW
-MAX_ITERATIONS = 8
-_MAX_NT = (1 << 32) - 2
-_MAX_BLOCKS = 1 << 18
 
 
 def _check_half_width(h):
@@ -55,16 +52,6 @@ def _check_half_width(h):
     return h
 
 
-def _check_nsigma(nsigma):
-    try:
-        v = float(nsigma)
-    except (TypeError, ValueError):
-        raise ValueError("nsigma must be a positive finite number, got %r" % (nsigma,))
-    if not (np.isfinite(v) and v > 0):
-        raise ValueError("nsigma must be a positive finite number, got %r" % (nsigma,))
-    return v
-
-
 def _check_grow(grow):
     grow = _int("grow", grow)
     if not 0 <= grow <= MAX_GROW:
@@ -72,118 +59,28 @@ def _check_grow(grow):
     return grow
 
 
-def _check_iterations(iterations):
-    iterations = _int("iterations", iterations)
-    if not 1 <= iterations <= MAX_ITERATIONS:
-        raise ValueError("iterations=%d outside [1, %d]" % (iterations, MAX_ITERATIONS))
-    return iterations
-
-
-def _check_sigma(sigma, nblocks):
-    """None, or the caller's sigma per block as a float64 array (>= 0 or +inf)."""
-    if sigma is None:
-        return None
-    if D.is_tensor(sigma):
-        sigma = D.to_host(sigma)
-    s = np.asarray(sigma, dtype=np.float64)
-    if s.ndim == 0:
-        s = np.full(nblocks, float(s))
-    if s.shape != (nblocks,):
-        raise ValueError("sigma must be one number or one per block (%d), got shape %s" % (nblocks, s.shape))
-    if not (s >= 0).all():                                   # NaN and negative values fail this
-        raise ValueError("every sigma must be >= 0 (or +inf)")
-    return np.ascontiguousarray(s)
-
-
-def _check_classes(name, cls, nt):
-    """A class array (uint8, NumPy or tensor) of nt samples."""
-    if D.is_tensor(cls):
-        if cls.dtype != D.torch.uint8 or cls.dim() != 1:
-            raise ValueError("%s must be a one-dimensional uint8 tensor, got %s %s" % (name, cls.dtype,
-                                                                                      tuple(cls.shape)))
-        n = int(cls.numel())
-    else:
-        a = np.asarray(cls)
-        if a.dtype != np.uint8 or a.ndim != 1:
-            raise ValueError("%s must be a one-dimensional uint8 array, got %s %s" % (name, a.dtype, a.shape))
-        n = int(a.size)
-    if n != nt:
-        raise ValueError("%s has %d samples, the stream %d" % (name, n, nt))
-
-
-class _Glitch(_hip.Handle):
+class _Glitch(_StageHandle):
     """Owns a cm2_glitch handle (block tables and the histograms of the selection)."""
-
-    def __init__(self, nt, sizes, half_width):
-        sz = np.ascontiguousarray(sizes, dtype=np.int64)
-        h = ctypes.c_void_p()
-        _hip.call("cm2_glitch_create", ctypes.byref(h), int(nt), sz.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
-                  len(sizes), int(half_width), D.stream())
-        _hip.Handle.__init__(self, "cm2_glitch_destroy", h)
-
-    def info(self):
-        info = (ctypes.c_int64 * 6)()
-        _hip.call("cm2_glitch_info", self.h, info)
-        return dict(zip(("nt", "nblocks", "half_width", "run", "tier", "bytes"), [int(v) for v in info]))
+    prefix, info_names = "glitch", ("nt", "nblocks", "half_width", "run", "tier", "bytes")
 
 
-class GlitchFlagger(object):
+class GlitchFlagger(_BlockStage):
     """
     Flags the glitches of time streams cut into the noise blocks ``blocksize`` (BlockLO's convention: an int that
     divides the stream, or the list of block sizes) with windows of ``2 half_width + 1`` samples,
     ``1 <= half_width <= 64``.  The object owns the block tables and the selection's histograms of the stream
     lengths it has met (8 KB per block), and no buffer of the stream's size.
     """
+    handle_class, window = _Glitch, "half_width"
+    noun, histograms = "glitch flagger", "the selection's histograms"
 
     def __init__(self, blocksize, half_width=16):
         self.half_width = _check_half_width(half_width)
-        if np.ndim(blocksize) == 0:
-            self.blocksize = _int("blocksize", blocksize)
-            if self.blocksize < 1:
-                raise ValueError("blocksize=%d < 1" % self.blocksize)
-        else:
-            self.blocksize = _block_sizes(blocksize, sum(_int("blocksize[%d]" % i, b)
-                                                         for i, b in enumerate(blocksize)))
-        self._handles = {}
-
-    # ---- checks (no GPU) ----
-    def _sizes(self, nt):
-        sizes = _block_sizes(self.blocksize, nt)
-        if nt > _MAX_NT:
-            raise ValueError("%d samples do not fit the 32-bit sample counts of the glitch flagger" % nt)
-        if len(sizes) > _MAX_BLOCKS:
-            raise ValueError("%d blocks are more than the %d the selection's histograms allow"
-                             % (len(sizes), _MAX_BLOCKS))
-        return sizes
-
-    def _check_stream(self, d, flags, prev=None):
-        nt = _tod_length(d)
-        if nt < 1:
-            raise ValueError("the TOD has no samples")
-        if flags is not None:
-            _check_flags(flags, nt)
-        _check_tod("d", d, nt)
-        if prev is not None:
-            _check_classes("prev", prev, nt)
-        return nt, self._sizes(nt)
-
-    # ---- device ----
-    def _handle(self, nt, sizes):
-        if nt not in self._handles:
-            self._handles[nt] = _Glitch(nt, sizes, self.half_width)
-        return self._handles[nt]
+        _BlockStage.__init__(self, blocksize)
 
     def info(self, nt):
         """The library's description of the handle for streams of ``nt`` samples (tier, run length, bytes owned)."""
-        sizes = self._sizes(_int("nt", nt))
-        D.require_gpu()
-        return self._handle(int(nt), sizes).info()
-
-    @staticmethod
-    def _dev_flags(flags):
-        if flags is None:
-            return None, 0
-        return _flags_to_dev(flags)
+        return _BlockStage.info(self, nt)
 
     def _residual(self, g, x, f, kind, prev, out=None):
         r = out if out is not None else D.empty(x.numel())

@@ -31,15 +31,13 @@ Every argument is checked before the GPU is touched (``ValueError``); without a 
 On several GPUs each rank corrects its own blocks: blocks are independent.
 """
 import collections
-import ctypes
 
 import numpy as np
 
 from .. import _hip
 from .. import device as D
-from .gap_fill import _check_flags, _check_out, _check_tod, _flags_to_dev
-from .glitches import _check_classes, _check_iterations, _check_nsigma, _check_sigma
-from .noise_model import _block_sizes, _int, _tod_length
+from ._stream_args import (_BlockStage, _StageHandle, _check_dev, _check_iterations, _check_nsigma, _check_out,
+                           _check_sigma, _int)
 
 __all__ = ["JumpCorrector", "correct_jumps", "JUMP_CLASSES"]
 
@@ -47,8 +45,6 @@ JUMP_CLASSES = ("clean", "jump", "near")
 CLEAN, AT, NEAR = range(3)
 MAX_WINDOW = 256               # CM2_JUMP_MAX_WINDOW
 MAX_RADIUS = 256               # CM2_JUMP_MAX_RADIUS
-_MAX_NT = (1 << 32) - 2
-_MAX_BLOCKS = 1 << 18
 
 JumpTable = collections.namedtuple("JumpTable", "positions heights offsets njumps total capacity counts_dev")
 JumpTable.__doc__ = """What :meth:`JumpCorrector.find` returns: ``positions`` (int64), ``heights`` and ``offsets``
@@ -86,69 +82,26 @@ def _check_capacity(capacity):
     return capacity
 
 
-def _check_dev(name, x, n, dtype):
-    """A tensor in HBM of n elements that an earlier call of this module returned."""
-    if not (D.is_tensor(x) and x.is_cuda and x.dim() == 1 and x.is_contiguous()):
-        raise ValueError("%s must be a contiguous one-dimensional tensor in HBM" % name)
-    if str(x.dtype) != "torch." + dtype or int(x.numel()) != n:
-        raise ValueError("%s must hold %d %s elements, got %d %s" % (name, n, dtype, x.numel(), x.dtype))
-
-
-class _Jump(_hip.Handle):
+class _Jump(_StageHandle):
     """Owns a cm2_jump handle (block tables, mark bytes, the select's storage and the scale's cm2_glitch)."""
-
-    def __init__(self, nt, sizes, half_window):
-        sz = np.ascontiguousarray(sizes, dtype=np.int64)
-        h = ctypes.c_void_p()
-        _hip.call("cm2_jump_create", ctypes.byref(h), int(nt), sz.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
-                  len(sizes), int(half_window), D.stream())
-        _hip.Handle.__init__(self, "cm2_jump_destroy", h)
-
-    def info(self):
-        info = (ctypes.c_int64 * 6)()
-        _hip.call("cm2_jump_info", self.h, info)
-        return dict(zip(("nt", "nblocks", "half_window", "tile", "lds_bytes", "bytes"), [int(v) for v in info]))
+    prefix, info_names = "jump", ("nt", "nblocks", "half_window", "tile", "lds_bytes", "bytes")
 
 
-class JumpCorrector(object):
+class JumpCorrector(_BlockStage):
     """
     Finds and removes the baseline jumps of time streams cut into the noise blocks ``blocksize`` (BlockLO's
     convention: an int that divides the stream, or the list of block sizes), comparing the means of the
     ``half_window`` samples on either side of every position, ``1 <= half_window <= 256``.  The object owns, per
     stream length it has met, the block tables, one byte per sample and the scale's histograms (8 KB per block).
     """
+    handle_class, window, prev_name = _Jump, "half_window", "classes"
+    noun, histograms = "jump corrector", "the scale's histograms"
 
     def __init__(self, blocksize, half_window=64):
         self.half_window = _check_window(half_window)
-        if np.ndim(blocksize) == 0:
-            self.blocksize = _int("blocksize", blocksize)
-            if self.blocksize < 1:
-                raise ValueError("blocksize=%d < 1" % self.blocksize)
-        else:
-            self.blocksize = _block_sizes(blocksize, sum(_int("blocksize[%d]" % i, b)
-                                                         for i, b in enumerate(blocksize)))
-        self._handles = {}
+        _BlockStage.__init__(self, blocksize)
 
     # ---- checks (no GPU) ----
-    def _sizes(self, nt):
-        sizes = _block_sizes(self.blocksize, nt)
-        if nt > _MAX_NT:
-            raise ValueError("%d samples do not fit the 32-bit sample counts of the jump corrector" % nt)
-        if len(sizes) > _MAX_BLOCKS:
-            raise ValueError("%d blocks are more than the %d the scale's histograms allow" % (len(sizes), _MAX_BLOCKS))
-        return sizes
-
-    def _check_stream(self, d, flags=None, prev=None):
-        nt = _tod_length(d)
-        if nt < 1:
-            raise ValueError("the TOD has no samples")
-        if flags is not None:
-            _check_flags(flags, nt)
-        _check_tod("d", d, nt)
-        if prev is not None:
-            _check_classes("classes", prev, nt)
-        return nt, self._sizes(nt)
-
     def _check_stat(self, t, noeval):
         if not D.is_tensor(t):
             raise ValueError("t must be the tensor that statistic() returned")
@@ -160,16 +113,9 @@ class JumpCorrector(object):
         return nt, self._sizes(nt)
 
     # ---- device ----
-    def _handle(self, nt, sizes):
-        if nt not in self._handles:
-            self._handles[nt] = _Jump(nt, sizes, self.half_window)
-        return self._handles[nt]
-
     def info(self, nt):
         """The library's description of the handle for streams of ``nt`` samples (tile, LDS bytes, bytes owned)."""
-        sizes = self._sizes(_int("nt", nt))
-        D.require_gpu()
-        return self._handle(int(nt), sizes).info()
+        return _BlockStage.info(self, nt)
 
     def _stat(self, g, x, f, kind, prev, min_count, t, noeval):
         _hip.call("cm2_jump_stat", g.h, D.ptr(x), D.ptr(f), kind, D.ptr(prev), min_count, D.ptr(t), D.ptr(noeval),
@@ -197,12 +143,6 @@ class JumpCorrector(object):
     def _correct(self, g, x, prev, table, radius, out, cls, counts):
         _hip.call("cm2_jump_correct", g.h, D.ptr(x), D.ptr(prev), D.ptr(table.positions), D.ptr(table.offsets),
                   D.ptr(table.counts_dev), table.capacity, radius, D.ptr(out), D.ptr(cls), D.ptr(counts), D.stream())
-
-    @staticmethod
-    def _dev_flags(flags):
-        if flags is None:
-            return None, 0
-        return _flags_to_dev(flags)
 
     @staticmethod
     def _out(out, x, d):

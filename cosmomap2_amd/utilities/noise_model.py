@@ -24,100 +24,10 @@ import numpy as np
 
 from .. import _hip
 from .. import device as D
+from ._stream_args import (_MIN_L, _block_sizes, _check_detrend, _check_fsample, _check_lam, _check_nperseg,
+                           _check_psd, _int, _tod_length)
 
 __all__ = ["noise_psd", "inverse_noise_bands", "estimate_inverse_noise"]
-
-_MIN_L, _MAX_L = 256, 65536
-
-
-def _is_pow2(n):
-    return n > 0 and (n & (n - 1)) == 0
-
-
-def _int(name, v):
-    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
-        raise ValueError("%s must be an integer, got %r" % (name, v))
-    return int(v)
-
-
-def _check_fsample(fsample):
-    try:
-        fs = float(fsample)
-    except (TypeError, ValueError):
-        raise ValueError("fsample must be a positive number, got %r" % (fsample,))
-    if not (np.isfinite(fs) and fs > 0):
-        raise ValueError("fsample must be a positive number, got %r" % (fsample,))
-    return fs
-
-
-def _check_nperseg(nperseg):
-    L = _int("nperseg", nperseg)
-    if not (_is_pow2(L) and _MIN_L <= L <= _MAX_L):
-        raise ValueError("nperseg=%d must be a power of two in [%d, %d]" % (L, _MIN_L, _MAX_L))
-    return L
-
-
-def _check_lam(lam, L):
-    lam = _int("lam", lam)
-    if not 1 <= lam <= L // 2:
-        raise ValueError("lam=%d outside [1, nperseg/2 = %d]" % (lam, L // 2))
-    return lam
-
-
-def _tod_length(d):
-    """Number of samples of a 1-D TOD (NumPy array or float64 tensor), without touching the GPU."""
-    if D.is_tensor(d):
-        if D.torch is None or d.dtype != D.torch.float64:
-            raise ValueError("a TOD tensor must be float64, got %s" % d.dtype)
-        if d.dim() != 1:
-            raise ValueError("the TOD must be one-dimensional, got shape %s" % (tuple(d.shape),))
-        return int(d.numel())
-    a = np.asarray(d)
-    if a.ndim != 1:
-        raise ValueError("the TOD must be one-dimensional, got shape %s" % (a.shape,))
-    if not (np.issubdtype(a.dtype, np.floating) or np.issubdtype(a.dtype, np.integer)):
-        raise ValueError("the TOD must be real numbers, got dtype %s" % a.dtype)
-    return int(a.size)
-
-
-def _block_sizes(blocksize, nt):
-    """Per-block sizes of ``blocksize`` (BlockLO's convention) for a TOD of ``nt`` samples."""
-    if np.ndim(blocksize) == 0:
-        bs = _int("blocksize", blocksize)
-        if bs <= 0 or nt % bs:
-            raise ValueError("blocksize=%d does not divide the %d samples of the TOD" % (bs, nt))
-        return [bs] * (nt // bs)
-    sizes = [_int("blocksize[%d]" % i, b) for i, b in enumerate(blocksize)]
-    if not sizes or any(s <= 0 for s in sizes):
-        raise ValueError("blocksize must list positive block sizes, got %r" % (list(blocksize),))
-    if sum(sizes) != nt:
-        raise ValueError("blocksize adds up to %d samples, the TOD has %d" % (sum(sizes), nt))
-    return sizes
-
-
-def _check_detrend(detrend):
-    if detrend is False:
-        return 0
-    if isinstance(detrend, str) and detrend == "constant":
-        return 1
-    raise ValueError("detrend must be 'constant' or False, got %r" % (detrend,))
-
-
-def _check_psd(psd):
-    """(nb, L) of a PSD array [nb, L/2+1] (NumPy array or float64 tensor)."""
-    if D.is_tensor(psd):
-        if psd.dtype != D.torch.float64:
-            raise ValueError("a PSD tensor must be float64, got %s" % psd.dtype)
-        shape = tuple(psd.shape)
-    else:
-        shape = np.shape(psd)
-    if len(shape) != 2 or shape[0] < 1:
-        raise ValueError("the PSD must be an array [nblocks, nperseg/2 + 1], got shape %s" % (shape,))
-    L = 2 * (shape[1] - 1)
-    if not (_is_pow2(L) and _MIN_L <= L <= _MAX_L):
-        raise ValueError("the PSD has %d bins per block: not nperseg/2 + 1 for a power of two nperseg in "
-                         "[%d, %d]" % (shape[1], _MIN_L, _MAX_L))
-    return shape[0], L
 
 
 class _Psd(_hip.Handle):

@@ -32,18 +32,11 @@ import numpy as np
 
 from .. import _hip
 from .. import device as D
-from .noise_model import _block_sizes, _check_fsample, _check_lam, _check_psd, _int
+from ._stream_args import _block_sizes, _check_fsample, _check_lam, _check_psd, _int, _u64
 
 __all__ = ["white_noise", "noise_filter_bands", "NoiseSimulator", "simulate_noise"]
 
 _KINDS = {"uniform": 0, "normal": 1}
-
-
-def _u64(name, v):
-    v = _int(name, v)
-    if not 0 <= v < 1 << 64:
-        raise ValueError("%s=%d outside [0, 2^64)" % (name, v))
-    return v
 
 
 def _check_kind(kind):

@@ -34,8 +34,9 @@ import numpy as np
 
 from .. import _hip
 from .. import device as D
-from .noise_model import (_MAX_L, _MIN_L, _block_sizes, _check_detrend, _check_fsample, _check_nperseg, _check_psd,
-                          _int, _tod_length, noise_psd)
+from ._stream_args import (_MAX_L, _MIN_L, _block_sizes, _check_detrend, _check_fsample, _check_nperseg, _check_psd,
+                           _int, _tod_length)
+from .noise_model import noise_psd
 
 __all__ = ["offset_prior_bands", "estimate_offset_prior"]
 

@@ -288,12 +288,14 @@ int main(int argc, char **argv)
                (int)check_flag_kind(atoi(argv[4]) != 0, atoi(argv[5])));
         return 0;
     }
-    // create nt h s0 s1 ...   (no sizes: a null pointer; ones: nt blocks of one sample)
+    // create nt h s0 s1 ...   (no sizes: a null pointer)
+    // ones n h [nt]             n blocks of one sample, nt = n unless given
     std::vector<int64_t> s;
     for (int i = 4; i < argc; ++i) s.push_back(atoll(argv[i]));
     if (!strcmp(argv[1], "ones")) s.assign((size_t)atoll(argv[2]), 1);
     Launch l;
-    const Status st = check_create(&l, atoll(argv[2]), s.empty() ? nullptr : s.data(), (int64_t)s.size(), atoi(argv[3]));
+    const int64_t nt = atoll(argv[!strcmp(argv[1], "ones") && argc > 4 ? 4 : 2]);
+    const Status st = check_create(&l, nt, s.empty() ? nullptr : s.data(), (int64_t)s.size(), atoi(argv[3]));
     printf("%d\n", (int)st);
     if (st != kOk || strcmp(argv[1], "create")) return 0;
     printf("%lld %lld %lld %lld %d %d %d %lld %lld %lld\n", (long long)l.nt, (long long)l.nblocks, (long long)l.runs,
@@ -396,6 +398,9 @@ def test_policy_status_codes(driver):
     assert create(100, 1, 100) == 0 and create(100, 64, 100) == 0
     assert create(2 ** 32 - 1, 4, 2 ** 32 - 1) == 4 and create(2 ** 32 - 2, 4, 2 ** 32 - 2) == 0   # kTooLarge
     assert _run(driver, "ones", (1 << 18) + 1, 4)[0] == ["5"] and _run(driver, "ones", 1 << 18, 4)[0] == ["0"]   # kTooManyBlocks
+    # two faults at once: size, then half-width, then the 32-bit limit, then the blocks, then their number
+    assert create(2 ** 32 - 1, 0, 2 ** 32 - 1) == 3 and create(0, 0, 1) == 1
+    assert _run(driver, "ones", (1 << 18) + 1, 4, (1 << 18) + 2)[0] == ["2"]
 
     def classify(nsigma, grow, have=0, kind=0):
         return [int(x) for x in _run(driver, "classify", nsigma, grow, have, kind)[0]]

@@ -369,12 +369,14 @@ int main(int argc, char **argv)
                (long long)table_upper(p.data(), (int64_t)p.size(), atoll(argv[2])));
         return 0;
     }
-    // create nt w s0 s1 ...   (no sizes: a null pointer; ones: nt blocks of one sample)
+    // create nt w s0 s1 ...   (no sizes: a null pointer)
+    // ones n w [nt]             n blocks of one sample, nt = n unless given
     std::vector<int64_t> s;
     for (int i = 4; i < argc; ++i) s.push_back(atoll(argv[i]));
     if (!strcmp(argv[1], "ones")) s.assign((size_t)atoll(argv[2]), 1);
     Launch l;
-    const Status st = check_create(&l, atoll(argv[2]), s.empty() ? nullptr : s.data(), (int64_t)s.size(), atoi(argv[3]));
+    const int64_t nt = atoll(argv[!strcmp(argv[1], "ones") && argc > 4 ? 4 : 2]);
+    const Status st = check_create(&l, nt, s.empty() ? nullptr : s.data(), (int64_t)s.size(), atoi(argv[3]));
     printf("%d\n", (int)st);
     if (st != kOk || strcmp(argv[1], "create")) return 0;
     printf("%lld %lld %lld %d %lld\n", (long long)l.nt, (long long)l.nblocks, (long long)l.tiles, l.w,
@@ -456,6 +458,9 @@ def test_policy_status_codes(driver):
     assert create(100, 1, 100) == 0 and create(100, 256, 100) == 0
     assert create(2 ** 32 - 1, 4, 2 ** 32 - 1) == 4 and create(2 ** 32 - 2, 4, 2 ** 32 - 2) == 0   # kTooLarge
     assert _run(driver, "ones", (1 << 18) + 1, 4)[0] == ["5"] and _run(driver, "ones", 1 << 18, 4)[0] == ["0"]
+    # two faults at once: size, then window, then the 32-bit limit, then the blocks, then their number
+    assert create(2 ** 32 - 1, 0, 2 ** 32 - 1) == 3 and create(0, 0, 1) == 1
+    assert _run(driver, "ones", (1 << 18) + 1, 4, (1 << 18) + 2)[0] == ["2"]
 
     def checks(w=8, have=0, kind=0, min_count=4, nsigma=6.0, capacity=10, radius=4):
         return [int(x) for x in _run(driver, "checks", w, have, kind, min_count, nsigma, capacity, radius)[0]]
@@ -531,3 +536,72 @@ def test_arguments_are_refused_before_the_gpu_is_needed():
                      lambda: correct_jumps(d, 50)):
             with pytest.raises(_hip.HipError):
                 call()
+
+
+# ------------------------------------------- which arrays of a call may share memory ----
+DISJOINT_DRIVER = r"""
+#include "cm2_stream_policy.h"
+#include <cstdio>
+#include <cstdlib>
+#include <vector>
+using namespace cm2::stream;
+// nout nin alias_out alias_in, then address and bytes of every output and of every input (address 0: NULL)
+int main(int argc, char **argv)
+{
+    if (argc < 5) return 2;
+    const int nout = atoi(argv[1]), nin = atoi(argv[2]);
+    if (argc != 5 + 2 * (nout + nin)) return 2;
+    std::vector<Range> r;
+    for (int i = 5; i < argc; i += 2)
+        r.push_back(Range{reinterpret_cast<const void *>((uintptr_t)strtoull(argv[i], nullptr, 10)),
+                          (uint64_t)strtoull(argv[i + 1], nullptr, 10)});
+    printf("%d\n", (int)disjoint(r.data(), nout, r.data() + nout, nin, atoi(argv[3]), atoi(argv[4])));
+    return 0;
+}
+"""
+
+
+@pytest.fixture(scope="module")
+def disjoint(tmp_path_factory):
+    d = tmp_path_factory.mktemp("stream_policy")
+    src = d / "disjoint.cpp"
+    src.write_text(DISJOINT_DRIVER)
+    exe = str(d / "disjoint")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I" + CSRC, str(src), "-o", exe])
+
+    def run(outs, ins, alias=(-1, -1)):
+        flat = [v for r in list(outs) + list(ins) for v in r]
+        return int(_run(exe, len(outs), len(ins), alias[0], alias[1], *flat)[0][0])
+    return run
+
+
+def test_disjoint_outputs_and_inputs(disjoint):
+    OK, ON_INPUT, ON_OUTPUT = 0, 1, 2
+    A, B, C = 1 << 20, 1 << 21, 1 << 22
+    assert disjoint([(A, 800)], [(B, 800), (C, 100)]) == OK
+    # a NULL range overlaps nothing, whatever its length, as an input and as an output
+    assert disjoint([(A, 800)], [(0, 1 << 40), (B, 8)]) == OK and disjoint([(0, 1 << 40), (A, 8)], [(A + 8, 8)]) == OK
+    assert disjoint([(0, 1 << 40)], [(0, 1 << 40)]) == OK
+    # adjacent: the last byte of one next to the first of the other, on either side
+    assert disjoint([(A, 800)], [(A + 800, 800)]) == OK and disjoint([(A, 800)], [(A - 800, 800)]) == OK
+    # one shared byte, on either side; a range inside the other; the same range
+    assert disjoint([(A, 800)], [(A + 799, 800)]) == ON_INPUT and disjoint([(A, 800)], [(A - 799, 800)]) == ON_INPUT
+    assert disjoint([(A, 800)], [(A + 8, 8)]) == ON_INPUT and disjoint([(A + 8, 8)], [(A, 800)]) == ON_INPUT
+    assert disjoint([(A, 800)], [(A, 800)]) == ON_INPUT
+    # every input is looked at, and every output
+    assert disjoint([(A, 800)], [(B, 8), (C, 8), (A + 792, 8)]) == ON_INPUT
+    assert disjoint([(B, 8), (A, 800)], [(C, 8), (A + 792, 8)]) == ON_INPUT
+    # output against output: adjacent, one shared byte, the last pair of three
+    assert disjoint([(A, 800), (A + 800, 100)], [(B, 8)]) == OK
+    assert disjoint([(A, 800), (A + 799, 100)], [(B, 8)]) == ON_OUTPUT
+    assert disjoint([(C, 8), (A, 800), (A + 799, 100)], []) == ON_OUTPUT
+    # the first pair in the order of the outputs decides: output 0 meets output 1 before output 1 meets an input
+    assert disjoint([(A, 800), (A + 8, 8)], [(A + 8, 8)]) == ON_INPUT
+    assert disjoint([(A, 800), (B, 8)], [(B, 8)]) == ON_INPUT and disjoint([(A, 800), (A, 8)], [(B, 8)]) == ON_OUTPUT
+    # the one pair that may alias: the same pointer only (cm2_jump_correct's d_out == d_in, 8-byte elements)
+    assert disjoint([(A, 800), (B, 100)], [(A, 800), (C, 100)], alias=(0, 0)) == OK
+    assert disjoint([(A, 800), (B, 100)], [(A + 8, 800), (C, 100)], alias=(0, 0)) == ON_INPUT
+    assert disjoint([(A, 800), (B, 100)], [(A - 8, 800), (C, 100)], alias=(0, 0)) == ON_INPUT
+    assert disjoint([(A, 800), (B, 100)], [(C, 100), (A, 800)], alias=(0, 0)) == ON_INPUT      # another input
+    assert disjoint([(B, 100), (A, 800)], [(A, 800), (C, 100)], alias=(0, 0)) == ON_INPUT      # another output
+    assert disjoint([(A, 800), (A, 100)], [(A, 800)], alias=(0, 0)) == ON_OUTPUT               # outputs never alias
