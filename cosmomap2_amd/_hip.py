@@ -177,9 +177,19 @@ PROTOTYPES = {
     "cm2_jump_scale": [_vp, _vp, _vp, _vp, _vp],
     "cm2_jump_find": [_vp, _vp, _vp, _vp, _dbl, _i64, _vp, _vp, _vp, _vp, _vp],
     "cm2_jump_correct": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _int, _vp, _vp, _vp, _vp],
+    "cm2_pca_create": [ctypes.POINTER(_vp), _i64, _int, _int, ctypes.POINTER(_i64), _i64, ctypes.POINTER(_i64), _int,
+                       _vp, _vp],
+    "cm2_pca_destroy": [_vp],
+    "cm2_pca_info": [_vp, ctypes.POINTER(_i64)],
+    "cm2_pca_cov_doubles": [_vp],
+    "cm2_pca_cov": [_vp, _vp, _vp, _vp, _vp],
+    "cm2_pca_set_modes": [_vp, _vp, _vp],
+    "cm2_pca_apply": [_vp, _vp, _vp, _vp],
+    "cm2_pca_fit": [_vp, _vp, _vp, _vp],
+    "cm2_pca_status": [_vp, _vp],
 }
 _RESTYPE = {"cm2_last_error": ctypes.c_char_p, "cm2_reduce_work_doubles": _i64,
-            "cm2_gemm_tn_work_doubles": _i64}
+            "cm2_gemm_tn_work_doubles": _i64, "cm2_pca_cov_doubles": _i64}
 
 _lib = None
 
@@ -234,7 +244,7 @@ ERR_OUT_OF_MEMORY = 3          # CM2_ERR_OUT_OF_MEMORY of include/cosmomap2.h
 # build frees what it had made) or overwrite their outputs from their inputs.  NOT in the list: the in-place
 # updates (cm2_axpy, cm2_scal, cm2_Z_axpy, cm2_panel_gemm with accumulate, cm2_pcg_update_*,
 # cm2_flag_samples, cm2_compact_*, cm2_noise_sim_draw with add, cm2_cmode_apply whose output may be its input,
-# cm2_glitch_apply_pix, cm2_jump_correct whose output may be its input),
+# cm2_glitch_apply_pix, cm2_jump_correct and cm2_pca_apply whose output may be its input),
 # which a second run would apply twice, and the drivers with callbacks (cm2_pcg, cm2_pcg_sharded, cm2_arnoldi).
 RESTARTABLE = frozenset([
     "cm2_pointing_create", "cm2_pointing_build_sell", "cm2_pointing_set_weights",
@@ -263,6 +273,7 @@ RESTARTABLE = frozenset([
     "cm2_glitch_create", "cm2_glitch_destroy", "cm2_glitch_info", "cm2_glitch_residual", "cm2_glitch_scale",
     "cm2_glitch_classify",
     "cm2_jump_create", "cm2_jump_destroy", "cm2_jump_info", "cm2_jump_stat", "cm2_jump_scale", "cm2_jump_find",
+    "cm2_pca_create", "cm2_pca_cov", "cm2_pca_set_modes", "cm2_pca_fit", "cm2_pca_status",
 ])
 
 

@@ -31,7 +31,8 @@ torch = D.torch
 __all__ = ["SparseLO", "ToeplitzLO", "BlockLO", "BlockDiagonalLO",
            "BlockDiagonalPreconditionerLO", "InverseLO", "CoarseLO", "DeflationLO",
            "TwoLevelPreconditionerLO", "FilterLO", "GroundFilterLO", "HWPSSFilterLO", "hwpss_plan",
-           "CommonModeFilterLO", "cmode_groups", "focalplane_modes", "set_pointing_mode", "lp"]
+           "CommonModeFilterLO", "cmode_groups", "focalplane_modes", "PCAFilterLO", "pca_select_modes",
+           "set_pointing_mode", "lp"]
 
 _I64P = ctypes.POINTER(ctypes.c_int64)
 _DBLP = ctypes.POINTER(ctypes.c_double)
@@ -1399,4 +1400,166 @@ class CommonModeFilterLO(_TimeFilter):
         detector), 2 few (fewer than ``K``), 3 pivot (collinear templates)."""
         out = D.empty(self.ngroups * self.ns, torch.uint8)
         _hip.call("cm2_cmode_status", self._handle.h, D.ptr(out))
+        return D.to_host(out).reshape(self.ngroups, self.ns)
+
+
+# ================================================================= PCAFilterLO ===
+PCA_MAX_K = 10               # CM2_PCA_MAX_K of include/cosmomap2.h
+
+
+def pca_select_modes(cov, K):
+    """``(modes [n, K], eigenvalues [n])`` of one symmetric covariance ``cov[n, n]`` (host, ``numpy.linalg.eigh``):
+    all eigenvalues in descending order, and the eigenvectors of the ``K`` largest as columns, each with its sign
+    fixed so that its component of largest magnitude (the first on a tie) is positive."""
+    w, v = np.linalg.eigh(np.asarray(cov, dtype=np.float64))
+    w, v = w[::-1], v[:, ::-1][:, :K]
+    top = np.argmax(np.abs(v), axis=0)
+    sign = np.where(v[top, np.arange(v.shape[1])] < 0, -1.0, 1.0)
+    return np.ascontiguousarray(v * sign), np.ascontiguousarray(w)
+
+
+class PCAFilterLO(_TimeFilter):
+    """
+    PCA filter: per group of detectors and time sample, fit ``K`` modes ``Phi_c[k, :]`` across the unflagged
+    detectors and subtract them, with modes that differ from chunk to chunk and are learnt from the data: the leading
+    eigenvectors of the detector-detector covariance of each chunk (include/cosmomap2.h, f2g).  No counterpart in
+    the reference.
+
+    ``PCAFilterLO(pix_samples, ndet, nmodes=1, groups=None, chunks=None, modes=None)``: ``pix_samples[ndet * ns]``
+    the pixel of every sample in the detector-major layout of ``expand_pointing`` (< 0 = flagged; an HBM int32 tensor
+    is adopted, not copied, and must not change afterwards); ``groups`` as :func:`cmode_groups` and ``chunks`` as
+    :func:`hwpss_plan` take them; modes can be set only when every group has at least ``nmodes + 1`` detectors (the
+    covariance is available for any grouping).  ``modes``
+    ``[nchunks, ndet, K]`` sets the modes at once (``nmodes`` is then ``K``); otherwise :meth:`learn` or
+    :meth:`set_modes` must be called before the operator is applied.
+
+    With fixed modes the operator is ``M - M Phi (Phi^T M Phi)^-1 Phi^T M`` sample by sample: linear, symmetric and
+    idempotent, so ``P.T * F * P`` is legitimate.  With modes learnt from ``d`` itself the stage as a whole,
+    ``d -> learn(d) -> F d``, is NOT linear in ``d``.  Zero-filled flagged samples break the low rank of the
+    atmosphere, so learn from a gap-filled stream with every sample used,
+    ``F.learn(fill_gaps_linear(d, pixs, [ns] * ndet), use_flags=False)``; the fit at apply time still honours the
+    flags.  A unit (group x sample) with fewer than ``K`` unflagged detectors, or whose modes are collinear on them,
+    is skipped as in :class:`CommonModeFilterLO`.
+    """
+    CLASSES = ("fitted", "empty", "few", "pivot")
+    _ENTRY = "cm2_pca_apply"
+
+    def __init__(self, pix_samples, ndet, nmodes=1, groups=None, chunks=None, modes=None):
+        self.edges = cmode_groups(ndet, groups)
+        self.ndet, self.ngroups = int(ndet), int(self.edges.size) - 1
+        if int(nmodes) != nmodes or not 1 <= int(nmodes) <= PCA_MAX_K:
+            raise ValueError("nmodes must be an integer in [1, %d], got %r" % (PCA_MAX_K, nmodes))
+        self.K = int(nmodes)
+        n = _size(pix_samples)
+        if n < self.ndet or n % self.ndet:
+            raise lp.ShapeError("pix_samples has %d entries, not a positive multiple of ndet = %d" % (n, self.ndet))
+        self.n, self.ns = n, n // self.ndet
+        self.chunk_edges = hwpss_plan(self.ns, chunks)
+        self.nchunks = int(self.chunk_edges.size) - 1
+        if modes is not None:
+            shape = tuple(modes.shape) if D.is_tensor(modes) else np.shape(modes)
+            if len(shape) != 3 or shape[:2] != (self.nchunks, self.ndet):
+                raise lp.ShapeError("modes must be [nchunks, ndet, K] = [%d, %d, K], got %r"
+                                    % (self.nchunks, self.ndet, tuple(shape)))
+            if not 1 <= shape[2] <= PCA_MAX_K:
+                raise ValueError("modes has K = %d columns, K must be in [1, %d]" % (shape[2], PCA_MAX_K))
+            if self.K not in (1, int(shape[2])):
+                raise ValueError("nmodes = %d but modes has K = %d columns" % (self.K, shape[2]))
+            self.K = int(shape[2])
+        self.sizes = [int(x) for x in np.diff(self.edges)]
+        if modes is not None:
+            self._check_group_sizes()
+        self.eigenvalues = None
+        self._modes = None
+        D.require_gpu()
+        self._d_pix = D.i32(pix_samples).reshape(-1)
+        handle = ctypes.c_void_p()
+        _hip.call("cm2_pca_create", ctypes.byref(handle), self.ns, self.ndet, self.ngroups,
+                  self.edges.ctypes.data_as(_I64P), self.nchunks, self.chunk_edges.ctypes.data_as(_I64P), self.K,
+                  D.ptr(self._d_pix), D.stream())
+        self._handle = _hip.Handle("cm2_pca_destroy", handle, keep=self._d_pix)
+        super(PCAFilterLO, self).__init__(nargin=self.n, nargout=self.n, matvec=self.mult, symmetric=True)
+        if modes is not None:
+            self.set_modes(modes)
+
+    @property
+    def modes(self):
+        """The modes in use, ``[nchunks, ndet, K]`` on the host (``None`` before any are set)."""
+        return self._modes
+
+    def _check_group_sizes(self):
+        if min(self.sizes) < self.K + 1:
+            raise ValueError("modes need at least nmodes + 1 = %d detectors in every group, the smallest has %d"
+                             % (self.K + 1, min(self.sizes)))
+
+    def set_modes(self, modes):
+        """Use ``modes[nchunks, ndet, K]`` (host array or tensor; copied) from now on."""
+        self._check_group_sizes()
+        shape = tuple(modes.shape) if D.is_tensor(modes) else np.shape(modes)
+        if tuple(shape) != (self.nchunks, self.ndet, self.K):
+            raise lp.ShapeError("modes must be [nchunks, ndet, K] = [%d, %d, %d], got %r"
+                                % (self.nchunks, self.ndet, self.K, tuple(shape)))
+        d_modes = D.f64(modes).reshape(-1)
+        _hip.call("cm2_pca_set_modes", self._handle.h, D.ptr(d_modes), D.stream())
+        self._modes = np.array(D.to_host(d_modes), dtype=np.float64).reshape(self.nchunks, self.ndet, self.K)
+
+    def covariance(self, d, use_flags=True):
+        """The detector-detector covariances of ``d``: a list over the chunks of lists over the groups of
+        ``[n_g, n_g]`` host arrays, ``sum_i x[a, i] x[b, i]`` over the chunk's samples, with flagged samples as
+        ``+0.0`` (``use_flags=False``: every sample is used)."""
+        x = self._input(d)
+        per = sum(n * n for n in self.sizes)
+        out = D.empty(self.nchunks * per)
+        _hip.call("cm2_pca_cov", self._handle.h, D.ptr(x), D.ptr(self._d_pix) if use_flags else None, D.ptr(out),
+                  D.stream())
+        flat = D.to_host(out)
+        cov, at = [], 0
+        for _ in range(self.nchunks):
+            row = []
+            for n in self.sizes:
+                row.append(flat[at:at + n * n].reshape(n, n).copy())
+                at += n * n
+            cov.append(row)
+        return cov
+
+    def learn(self, d, use_flags=True):
+        """Learn the modes from ``d``: the covariance on the GPU, then per (chunk, group) the eigenvectors of its
+        ``K`` largest eigenvalues (:func:`pca_select_modes`, on the host), and :meth:`set_modes`.  All eigenvalues
+        are kept, descending, as ``self.eigenvalues[chunk][group]``.  Returns ``self``."""
+        self._check_group_sizes()
+        cov = self.covariance(d, use_flags)
+        bad = [(c, g) for c in range(self.nchunks) for g in range(self.ngroups) if not np.isfinite(cov[c][g]).all()]
+        if bad:
+            raise ValueError("the covariance of %d (chunk, group) units is not finite: %s%s"
+                             % (len(bad), ", ".join("(%d, %d)" % u for u in bad[:8]), " ..." if len(bad) > 8 else ""))
+        modes = np.zeros((self.nchunks, self.ndet, self.K))
+        eig = []
+        for c in range(self.nchunks):
+            eig.append([])
+            for g in range(self.ngroups):
+                m, w = pca_select_modes(cov[c][g], self.K)
+                modes[c, self.edges[g]:self.edges[g + 1]] = m
+                eig[c].append(w)
+        self.eigenvalues = eig
+        self.set_modes(modes)
+        return self
+
+    def filter_info(self):
+        info = (ctypes.c_int64 * 13)()
+        _hip.call("cm2_pca_info", self._handle.h, info)
+        names = ("ns", "ndet", "ngroups", "nchunks", "K", "cov_doubles", "work_doubles", "work_items", "modes_set")
+        return dict(zip(names + self.CLASSES, [int(v) for v in info]))
+
+    def coefficients(self, d):
+        """The fitted coefficients ``[ngroups, K, ns]`` of ``d`` (zeros for a skipped unit): the mode time streams;
+        nothing is subtracted."""
+        x = self._input(d)
+        out = D.empty(self.ngroups * self.K * self.ns)
+        _hip.call("cm2_pca_fit", self._handle.h, D.ptr(x), D.ptr(out), D.stream())
+        return D.like_input(out, d).reshape(self.ngroups, self.K, self.ns)
+
+    def status(self):
+        """The class of every unit, ``[ngroups, ns]`` uint8 on the host: 0 fitted, 1 empty, 2 few, 3 pivot."""
+        out = D.empty(self.ngroups * self.ns, torch.uint8)
+        _hip.call("cm2_pca_status", self._handle.h, D.ptr(out))
         return D.to_host(out).reshape(self.ngroups, self.ns)

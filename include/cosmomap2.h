@@ -804,6 +804,80 @@ int cm2_jump_correct(cm2_jump *h, const double *d_in, const uint8_t *d_prev, con
                      const double *d_offsets, const int64_t *d_njumps, int64_t capacity, int radius, double *d_out,
                      uint8_t *d_class, int64_t *d_counts, void *stream);
 
+/* ---- f2g: PCA filter  (PCAFilterLO) ------------------------------------------------------------
+ * Removes modes across the detectors that are learnt from the data and change from chunk to chunk: the
+ * detector-detector covariance of a stretch of data, its leading eigenvectors as the templates, and f2d's fit and
+ * removal of them sample by sample.  The eigenproblem is the caller's (PCAFilterLO.learn solves it on the host);
+ * the library computes the covariance and applies modes it is given.  No counterpart in the reference.
+ * Layout as in f2d: nt = ndet ns, sample i of detector k at k ns + i, flagged where d_pix[nt] < 0, the group edges
+ * 0 = g_0 < ... < g_G = ndet.  New here are the chunk edges 0 = c_0 < ... < c_C = ns, and 1 <= K <= CM2_PCA_MAX_K.
+ *
+ * Covariance, one unit per (chunk c, group g), n = g_{g+1} - g_g detectors a, b counted from g_g:
+ *     x[a, i] = d[(g_g + a) ns + i], or +0.0 where d_flags is given and d_flags[(g_g + a) ns + i] < 0
+ *     (d_flags NULL: every sample is used; a flagged sample's value is never read),
+ *     Cov_u[a n + b] = sum_{i = c_c}^{c_{c+1} - 1} x[a, i] x[b, i].
+ * Units are stored chunk-major, then by group: off(c, g) = c sum_g n_g^2 + sum_{g' < g} n_g'^2; cm2_pca_cov_doubles is
+ * C sum_g n_g^2.  Stored entries are exactly symmetric: entry (a, b) with a >= b is formed and (b, a) is its copy.
+ * Order (no floating-point atomics; the bits do not depend on the run, on ns, on the other chunks or on the other
+ * groups, only on the unit's own samples and on the chunk's length): the chunk is cut, from its own first sample,
+ * into segments of CM2_PCA_SEGMENT samples (the last one shorter).  Within a segment an entry is one accumulator that
+ * starts at +0.0 and takes one v_mfma_f64_16x16x4_f64 per four consecutive samples, in ascending i (the last
+ * instruction of a segment is padded with +0.0 samples); how the four products of one instruction are added to the
+ * accumulator is the hardware's.  The entry is then p_0 + p_1 + ... + p_{S-1}, the segment partials added from left
+ * to right.  Rows beyond the group (the 128-row tiles and 16-row MFMA blocks are padded with +0.0 rows) are never
+ * stored.  A non-finite used sample of detector a makes row and column a of its own unit non-finite and nothing
+ * else.  A unit whose samples are all flagged is exactly 0.
+ *
+ * Modes: Phi_c[k, 0..K-1] per chunk and detector, d_modes[(c ndet + k) K + j].
+ *
+ * Apply, one unit per (group, time sample i), i in chunk c: exactly f2d's unit with Phi = Phi_c.  Gram sums
+ * G_ab += Phi_ka Phi_kb, b_a += Phi_ka v[k, i] over the unflagged detectors of the group in ascending k; cm2_fit.h's
+ * factor, its pivot rule with tau = CM2_PCA_TAU = 2^-10 and its two solves; the projection
+ * out[k, i] = v[k, i] - (((c_0 Phi_k0 + c_1 Phi_k1) + ...) + c_{K-1} Phi_k,K-1) in ascending j; flagged samples and
+ * every sample of a skipped unit are 0; the classes are CM2_PCA_FITTED, _EMPTY (m = 0), _FEW (0 < m < K) and _PIVOT.
+ * Every product and sum is rounded on its own (-ffp-contract=off).  Given fixed modes the operator is
+ * M - M Phi (Phi^T M Phi)^-1 Phi^T M sample by sample: symmetric and idempotent.  With modes learnt from d itself
+ * the stage as a whole is not linear in d.
+ *
+ * cm2_pca_create keeps d_pix (it must not change or be freed while the handle lives) and copies the edges; builds the
+ *   work-item and slab tables and the covariance workspace.  Allocates and synchronises.  No modes are set yet.
+ * cm2_pca_info: h_info[13] = ns, ndet, ngroups, nchunks, K, covariance doubles, workspace doubles, covariance work
+ *   items, 1 when modes are set, units fitted, empty, few, pivot (0 before modes are set).
+ * cm2_pca_cov_doubles: the doubles cm2_pca_cov writes (-1 for a NULL handle).
+ * cm2_pca_cov: d_cov = the covariances of d_in; d_flags NULL or nt int32.  Two launches in the handle's own
+ *   workspace, no allocation, no synchronisation.  Two calls on one handle must not run at the same time.
+ * cm2_pca_set_modes copies d_modes[nchunks ndet K], classes every unit and counts the classes.  Synchronises.
+ *   Refused when a group has fewer than K + 1 detectors (K modes on K detectors would remove everything); the
+ *   covariance of such a handle is still available.
+ * cm2_pca_apply: d_out = F d_in (nt doubles each).  One launch, no allocation, no synchronisation.  d_out may be d_in
+ *   itself (a thread reads its column before it stores and touches no other); any other overlap is refused.
+ * cm2_pca_fit: d_coeff[(g K + j) ns + i] = c_j of unit (g, i), 0 for a skipped unit: the mode time streams.
+ * cm2_pca_status: d_status[g ns + i] = the class of unit (g, i), one byte each.  Synchronises.
+ * Refused with CM2_ERR_ARGUMENT, the outputs (and *out) untouched: K outside [1, 10]; ns, ndet, ngroups or nchunks
+ * < 1; group edges that do not ascend strictly from 0 to ndet; chunk edges that do not ascend strictly from 0 to ns;
+ * modes for a handle with a group of fewer than K + 1 detectors; NULL pointers (but d_flags); sizes that overflow the index types or a grid
+ * (ndet ns > 2^46, ndet > 2^23, nchunks > 2^16, 2^31 or more workgroups in a launch); d_cov sharing memory with d_in
+ * or d_flags; d_out overlapping d_in without being d_in; d_coeff sharing memory with d_in; apply, fit or status
+ * before modes are set. */
+#define CM2_PCA_TAU 0.0009765625            /* 2^-10 */
+#define CM2_PCA_MAX_K 10
+#define CM2_PCA_SEGMENT 4096
+#define CM2_PCA_FITTED 0
+#define CM2_PCA_EMPTY 1
+#define CM2_PCA_FEW 2
+#define CM2_PCA_PIVOT 3
+typedef struct cm2_pca cm2_pca;
+int cm2_pca_create(cm2_pca **out, int64_t ns, int ndet, int ngroups, const int64_t *h_group_edges, int64_t nchunks,
+                   const int64_t *h_chunk_edges, int K, const int32_t *d_pix, void *stream);
+int cm2_pca_destroy(cm2_pca *h);
+int cm2_pca_info(const cm2_pca *h, int64_t *h_info);
+int64_t cm2_pca_cov_doubles(const cm2_pca *h);
+int cm2_pca_cov(cm2_pca *h, const double *d_in, const int32_t *d_flags, double *d_cov, void *stream);
+int cm2_pca_set_modes(cm2_pca *h, const double *d_modes, void *stream);
+int cm2_pca_apply(cm2_pca *h, const double *d_in, double *d_out, void *stream);
+int cm2_pca_fit(cm2_pca *h, const double *d_in, double *d_coeff, void *stream);
+int cm2_pca_status(const cm2_pca *h, uint8_t *d_status);
+
 /* ---- f3: solution vector <-> full-sky HEALPix maps -------------------------------
  * cm2_cutsky_to_fullsky: d_full is pol arrays of nfull doubles one after the other
  * ([I | Q | U]); component k of observed pixel i, d_map[pol*i + k], goes to
