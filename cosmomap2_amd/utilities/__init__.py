@@ -12,3 +12,4 @@ from .gap_fill import *                                      # noqa: F401,F403
 from .pointing_expand import *                               # noqa: F401,F403
 from .glitches import *                                      # noqa: F401,F403
 from .jumps import *                                         # noqa: F401,F403
+from .demodulate import *                                   # noqa: F401,F403

@@ -878,6 +878,69 @@ int cm2_pca_apply(cm2_pca *h, const double *d_in, double *d_out, void *stream);
 int cm2_pca_fit(cm2_pca *h, const double *d_in, double *d_coeff, void *stream);
 int cm2_pca_status(const cm2_pca *h, uint8_t *d_status);
 
+/* ---- f2h: demodulation and decimation  (Demodulator, demodulate, decimate, lowpass_taps) ----------
+ * Lock-in demodulation of a stream modulated by a rotating half-wave plate: the stream and its products with the
+ * polarisation carrier cos 2 phi, sin 2 phi (cm2_pointing_expand writes it) are low-passed by a FIR filter and one
+ * sample in D is kept, which gives three slow streams T, Q, U that map with a plain pol = 1 pointing.  Without a
+ * carrier the same kernel decimates.  No counterpart in the reference: the definition is the one below, and every
+ * result has the bits it gives, on every run and every layout of threads.
+ * Inputs: d[nt]; noise blocks of sizes[0..nblocks-1] samples adding up to nt (BlockLO's convention), block b the n_b
+ * samples [start_b, end_b); the factor 1 <= D <= CM2_DEMOD_MAX_FACTOR; the taps h[0..L-1], L odd, 1 <= L <=
+ * CM2_DEMOD_MAX_TAPS, c = (L - 1) / 2, every tap finite, Wfull = the taps added from 0.0 in ascending k finite and > 0;
+ * optional flags in the two encodings of cm2_gaps_create (flag_kind 0: int32, flagged when negative; 1: bytes, flagged
+ * when non-zero; d_flags NULL: nothing flagged); optionally the carrier cosv[nt], sinv[nt]; min_weight in (0, 1].
+ * Everything is cut at the block boundaries.  Every operation on doubles named below is rounded once (no fused
+ * multiply-add).
+ * Outputs: block b gives m_b = ceil(n_b / D) outputs, output j centred on sample j D of the block; the output streams
+ * are the blocks one after the other, M = sum m_b.
+ *  1. usable_i: the sample is not flagged and d_i is finite.  cosv and sinv are used only at usable samples: what
+ *     they hold elsewhere (a NaN) changes nothing.  (They may be loaded there: both arrays are nt doubles.)
+ *  2. The terms of output j of block b: k = 0 .. L - 1 in ascending order, i = j D - c + k counted from start_b.  A
+ *     term is included when 0 <= i < n_b and sample i is usable.
+ *  3. The chains: sT = sQ = sU = W = 0.0; for each included term, in this association,
+ *         sT = sT + h_k d_i,  sQ = sQ + h_k (d_i cosv_i),  sU = sU + h_k (d_i sinv_i),  W = W + h_k.
+ *     (An excluded term may be added as h_k 0.0 = +-0.0: a chain that started at +0.0 never holds -0.0, so its bits do
+ *     not change.  A unit with every term included has W = Wfull, the same additions.)
+ *  4. Weight test: W >= min_weight Wfull (one multiplication; false for a NaN).  Passed: T_j = sT / W,
+ *     Q_j = 2.0 (sQ / W), U_j = 2.0 (sU / W).  Failed: T_j = Q_j = U_j = +0.0.
+ *  5. The class byte: CM2_DEMOD_FULL when all L terms were included; otherwise CM2_DEMOD_PARTIAL when the weight test
+ *     passed; otherwise CM2_DEMOD_REJECTED.  counts[b][3], int64: the outputs of block b per class.
+ *  6. Without a carrier only T, the classes and the counts exist.
+ * Truncated windows bias the result by far more than W / Wfull suggests (the carrier is no longer averaged over whole
+ * periods): PARTIAL outputs are for inspection, maps should take FULL ones (cm2_demod_pick with drop_from = 1).  Gaps
+ * should be filled (cm2_gaps_fill_linear, GapFiller) before demodulating: a normalised sum across a gap leaks
+ * intensity into Q and U.
+ *
+ * cm2_demod_create copies h_sizes and h_taps; the handle owns the block tables of the input units and the output
+ *   prefix, and the taps on the device.  Allocates and synchronises.
+ * cm2_demod_info: h_info[9] = nt, nblocks, D, L, M, input samples per workgroup, outputs per thread, LDS bytes of a
+ *   workgroup with a carrier, bytes owned.
+ * cm2_demod_run: d_T[M], d_class[M] (one byte each), d_counts[nblocks][3] and, with a carrier (d_cos and d_sin both
+ *   given), d_Q[M] and d_U[M]; without one d_cos, d_sin, d_Q and d_U are all NULL.  One memset and one launch, no
+ *   allocation, no synchronisation.
+ * cm2_demod_pick: d_out[M] (int32) = d_pix[centre sample of the output], or -1 where d_class >= drop_from (1: keep
+ *   FULL only; 2: keep FULL and PARTIAL) or the centre pixel is negative.  One launch.
+ * Refused with CM2_ERR_ARGUMENT, the outputs (and *out) untouched: D outside [1, 64]; nt < 1 or nt >= 2^32 - 1; sizes
+ * that are not positive or do not add up to nt; more than 2^18 blocks; an even L, L outside [1, 1025]; a tap that is
+ * not finite; Wfull not finite or <= 0; NULL pointers (d_flags may be NULL; the carrier and Q, U as above); a
+ * flag_kind other than 0 or 1 with flags given; min_weight outside (0, 1]; drop_from other than 1 or 2; an output that
+ * overlaps an input or another output. */
+#define CM2_DEMOD_MAX_FACTOR 64
+#define CM2_DEMOD_MAX_TAPS 1025
+#define CM2_DEMOD_FULL 0
+#define CM2_DEMOD_PARTIAL 1
+#define CM2_DEMOD_REJECTED 2
+typedef struct cm2_demod cm2_demod;
+int cm2_demod_create(cm2_demod **out, int64_t nt, const int64_t *h_sizes, int64_t nblocks, int factor,
+                     const double *h_taps, int ntaps, void *stream);
+int cm2_demod_destroy(cm2_demod *h);
+int cm2_demod_info(const cm2_demod *h, int64_t *h_info);
+int cm2_demod_run(cm2_demod *h, const double *d_in, const double *d_cos, const double *d_sin, const void *d_flags,
+                  int flag_kind, double min_weight, double *d_T, double *d_Q, double *d_U, uint8_t *d_class,
+                  int64_t *d_counts, void *stream);
+int cm2_demod_pick(const cm2_demod *h, const int32_t *d_pix, const uint8_t *d_class, int drop_from, int32_t *d_out,
+                   void *stream);
+
 /* ---- f3: solution vector <-> full-sky HEALPix maps -------------------------------
  * cm2_cutsky_to_fullsky: d_full is pol arrays of nfull doubles one after the other
  * ([I | Q | U]); component k of observed pixel i, d_map[pol*i + k], goes to
