@@ -97,7 +97,7 @@ __global__ __launch_bounds__(256) void k_psd_finish(const int64_t *__restrict__ 
 }
 
 // G[b][k] = 1 / S_k with S_k = P_k fs / m_k and S_0 := S_1.  The first (block, bin) whose S is not positive
-// and finite goes to *bad (flat index b * nfreq + k, the smallest one wins).
+// and finite, or so small that 1 / S overflows, goes to *bad (flat index b * nfreq + k, the smallest one wins).
 __global__ __launch_bounds__(256) void k_bands_inverse(const double *__restrict__ psd, int64_t nb, int64_t nfreq,
                                                         double fs, double *__restrict__ G,
                                                         unsigned long long *__restrict__ bad)
@@ -108,8 +108,9 @@ __global__ __launch_bounds__(256) void k_bands_inverse(const double *__restrict_
     const int64_t kk = k == 0 ? 1 : k;
     const double m = (kk == nfreq - 1) ? 1.0 : 2.0;
     const double S = psd[b * nfreq + kk] * fs / m;
-    if (!(S > 0.0) || !isfinite(S)) atomicMin(bad, (unsigned long long)(b * nfreq + kk));
-    G[i] = 1.0 / S;
+    const double g = 1.0 / S;
+    if (!(S > 0.0) || !isfinite(S) || !isfinite(g)) atomicMin(bad, (unsigned long long)(b * nfreq + kk));
+    G[i] = g;
 }
 
 // G[b][k] = sqrt(S_k), same S.  Zero is allowed; the first (block, bin) whose S is negative or not finite

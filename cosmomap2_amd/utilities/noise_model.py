@@ -92,8 +92,9 @@ def inverse_noise_bands(psd, lam, fsample=1.0):
 
     The Bartlett taper makes the band's symbol G smoothed by the Fejer kernel, which is >= 0: every
     block built from ``a`` is SPD, with no positivity lift.  White noise of variance s^2 gives
-    ``a ~ (1/s^2, 0, ...)``; ``lam = 1`` gives one white-noise weight per block.  A bin with S <= 0
-    or not finite raises ``ValueError`` naming the block and the bin.
+    ``a ~ (1/s^2, 0, ...)``; ``lam = 1`` gives one white-noise weight per block.  ``S`` must be
+    positive, finite and not so small that ``1/S`` overflows: any other bin raises ``ValueError``
+    naming the block and the bin.
     """
     nb, L = _check_psd(psd)
     lam = _check_lam(lam, L)

@@ -976,8 +976,9 @@ int cm2_psd_welch(cm2_psd *p, const double *d_tod, const int64_t *h_sizes, int64
  * S_k = P_k fs / m_k (m_k = 1 at k = 0 and L/2, else 2), S_0 := S_1, G = 1/S,
  * c_j = irfft(G, L)[j] as a cosine sum over k in increasing order, a_j = (1 - j/lambda) c_j (Bartlett:
  * the band's symbol is G smoothed by the Fejer kernel, so every block is SPD).  A bin with S <= 0 or
- * not finite fails with CM2_ERR_ARGUMENT and a message naming the block and the bin (the first in
- * block-major order).  Overwrites d_bands; synchronises. */
+ * not finite, or so small that 1/S overflows, fails with CM2_ERR_ARGUMENT and a message naming the block
+ * and the bin (the first in block-major order; d_bands is then left untouched).  Overwrites d_bands;
+ * synchronises. */
 int cm2_noise_bands_from_psd(const double *d_psd, int64_t nb, int64_t nperseg, double fsample,
                              int64_t lambda, double *d_bands, void *stream);
 
