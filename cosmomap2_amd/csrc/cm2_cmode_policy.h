@@ -10,38 +10,32 @@
 #pragma once
 #include <cstdint>
 
-#include "cm2_fit.h"
+#include "cm2_modefit_policy.h"
 
 namespace cm2 {
 namespace cmode {
 
-constexpr int kThreads = 256;              // threads of a workgroup = units of a workgroup
-constexpr int kMaxK = 10;                  // templates per detector (the monomials of total degree <= 3)
-
-// the classes of a unit, as cm2_cmode_status reports them
-enum Class { kFitted = 0, kEmpty = 1, kFew = 2, kPivot = 3 };
-
-enum Status { kOk = 0, kBadK = 1, kBadSize = 2, kBadEdges = 3, kTooLarge = 4 };
-
-// (constexpr: callable from device code as well)
-using fit::packed;          // doubles of the lower triangle
-using fit::packed_at;       // entry (i, j), j <= i
+// the workgroup, the largest K, the classes of a unit, the status codes and apply_ok: shared with the PCA filter
+using modefit::kThreads;
+using modefit::kMaxK;
+using modefit::Class, modefit::kFitted, modefit::kEmpty, modefit::kFew, modefit::kPivot;
+using modefit::Status, modefit::kOk, modefit::kBadK, modefit::kBadSize, modefit::kBadEdges, modefit::kTooLarge;
+using modefit::packed;
+using modefit::packed_at;
+using modefit::apply_ok;
 constexpr int64_t blocks_per_group(int64_t ns) { return (ns + kThreads - 1) / kThreads; }
 
 struct Launch {
     int64_t blocks_per_group = 0, blocks = 0, units = 0, nt = 0;
 };
 
-// fills *l; anything but kOk leaves it unspecified.  The limits keep every sample index (ndet ns <= 2^46) and every
-// coefficient index (ngroups K ns <= 10 x 2^46) below 2^63, and the workgroup count (a grid dimension) below 2^31.
+// fills *l; anything but kOk leaves it unspecified.  Beyond the shared limits, the workgroup count (a grid dimension)
+// stays below 2^31.
 inline Status check(Launch *l, int64_t ns, int64_t ndet, int64_t ngroups, const int64_t *edges, int K)
 {
-    if (K < 1 || K > kMaxK) return kBadK;
-    if (ns < 1 || ndet < 1 || ngroups < 1 || !edges) return kBadSize;
-    if (!fit::edges_ok(edges, ngroups, ndet)) return kBadEdges;
+    const Status shared = modefit::check(ns, ndet, ngroups, edges, K);
+    if (shared != kOk) return shared;
     const int64_t lim = (int64_t)1 << 31;
-    if (ndet >= lim) return kTooLarge;
-    if (ndet > (((int64_t)1 << 46) / ns)) return kTooLarge;
     const int64_t b = blocks_per_group(ns);
     if (ngroups > (lim - 1) / b) return kTooLarge;
     l->blocks_per_group = b;

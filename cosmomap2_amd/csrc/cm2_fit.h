@@ -1,7 +1,8 @@
-// cm2_fit.h -- the small least-squares fit of the time-stream filters (cm2_hwpss.hip, cm2_cmode.hip), written once:
-// the Cholesky factor with its pivot rule, the two triangular solves, the packed lower triangle and the rule of an
-// edge list.  Plain C++17 with no HIP include of its own: the kernels inline it, and tests/test_fit_header_cpu.py
-// compiles it with the host compiler and compares it bit for bit with tests/_fit_ref.py.
+// cm2_fit.h -- the small least-squares fit of the time-stream filters (cm2_hwpss.hip, and cm2_modefit.h for
+// cm2_cmode.hip and cm2_pca.hip), written once: the Cholesky factor with its pivot rule, the two triangular solves,
+// the packed lower triangle and the rule of an edge list.  Plain C++17 with no HIP include of its own: the kernels
+// inline it, and tests/test_fit_header_cpu.py compiles it with the host compiler and compares it bit for bit with
+// tests/_fit_ref.py.
 //
 // The order of every operation (compile with -ffp-contract=off: every product and every sum is rounded on its own):
 //   Factor: G = L L^T, row by row, p_j = G_jj - L_j0^2 - ... - L_j,j-1^2 (left to right); the pivot fails when

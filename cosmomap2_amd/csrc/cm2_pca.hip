@@ -15,16 +15,18 @@
 // k_pca_cov_final: one thread per stored entry (a, b); it adds the partials of the segments of entry
 // (max(a, b), min(a, b)) in ascending segment order, starting from segment 0's, so both mirrors get the same bits.
 //
-// Apply, fit and class: cm2_cmode.hip's unit restated with Phi = the modes of the sample's chunk; a workgroup is one
-// slab of the policy's table, so the chunk and with it Phi_c[k, :] is the same for the whole workgroup.  The order
-// of every operation is the one written in cm2_cmode.hip (steps 1 to 3), compiled with -ffp-contract=off.
+// Apply, fit and class: the unit of cm2_modefit.h (shared with the common-mode filter) with Phi = the modes of the
+// sample's chunk; a workgroup is one slab of the policy's table, so the chunk and with it Phi_c[k, :] is the same for
+// the whole workgroup.  The order of every operation is the one written in cm2_modefit.h (steps 1 to 3), compiled
+// with -ffp-contract=off.
 #include <vector>
 
-#include "cm2_common.h"
+#include "cm2_modefit.h"
 #include "cm2_pca_policy.h"
 
 using namespace cm2;
 namespace pp = cm2::pca;
+namespace mf = cm2::modefit;
 
 typedef double double4_t __attribute__((ext_vector_type(4)));
 static_assert(pp::kSegment == CM2_PCA_SEGMENT && pp::kMaxK == CM2_PCA_MAX_K, "the header states the policy's constants");
@@ -169,168 +171,42 @@ struct Shape {
     const int32_t *pix;             // [ndet ns], device, borrowed
 };
 
-// the unit of this thread: group g, sample i (i < 0: none), detectors [k0, k1), the modes of its chunk
-struct Unit {
-    int64_t g, i;
-    int k0, k1;
-    const double *phi;              // Phi_c[0, 0]
-};
-
+// the unit of this thread: its slab gives the sample and the chunk, the chunk the modes
 template <int K>
-__device__ __forceinline__ Unit my_unit(const Shape &s)
+__device__ __forceinline__ mf::Frame my_unit(const Shape &s)
 {
-    Unit u;
+    mf::Frame u;
+    u.ns = s.ns;
     u.g = (int64_t)blockIdx.x / s.nslabs;
     const pp::Slab sl = s.slabs[(int64_t)blockIdx.x - u.g * s.nslabs];
-    u.i = (int)threadIdx.x < sl.len ? sl.first + threadIdx.x : -1;
+    u.i = (int)threadIdx.x < sl.len ? sl.first + threadIdx.x : -1;      // past the slab's end: not the next slab's
     u.k0 = s.gedges[u.g];
     u.k1 = s.gedges[u.g + 1];
     u.phi = s.modes + (int64_t)sl.chunk * s.ndet * K;
+    u.pix = s.pix;
+    u.live = u.i >= 0;
     return u;
 }
 
-// detectors whose loads a thread keeps in flight (cm2_cmode.hip says why)
-template <int K>
-constexpr int kAhead = K <= 6 ? 8 : 4;
-
-template <int K>
-using KConst = std::integral_constant<int, K>;
-
-// step 1.  WITH_B = false: G and m only (the class of a unit depends on Phi_c and the flags alone)
-template <int K, bool WITH_B>
-__device__ __forceinline__ int gram(const Shape &s, const Unit &u, const double *v, double (&G)[pp::packed(K)],
-                                    double (&b)[K])
-{
-#pragma unroll
-    for (int e = 0; e < pp::packed(K); ++e) G[e] = 0.0;
-#pragma unroll
-    for (int a = 0; a < K; ++a) b[a] = 0.0;
-    int m = 0;
-    auto take = [&](int k, int32_t px, double x) {
-        if (px >= 0) {
-            const double *__restrict__ ph = u.phi + (int64_t)k * K;
-            ++m;
-#pragma unroll
-            for (int a = 0; a < K; ++a) {
-                const double fa = ph[a];
-#pragma unroll
-                for (int c = 0; c <= a; ++c) G[pp::packed_at(a, c)] += fa * ph[c];
-                if (WITH_B) b[a] += fa * x;
-            }
-        }
-    };
-    int k = u.k0;
-    for (; k + kAhead<K> <= u.k1; k += kAhead<K>) {
-        int32_t px[kAhead<K>];
-        double x[kAhead<K>];
-#pragma unroll
-        for (int j = 0; j < kAhead<K>; ++j) {
-            const int64_t at = (int64_t)(k + j) * s.ns + u.i;
-            px[j] = s.pix[at];
-            x[j] = WITH_B ? v[at] : 0.0;
-        }
-#pragma unroll
-        for (int j = 0; j < kAhead<K>; ++j) take(k + j, px[j], x[j]);
-    }
-    for (; k < u.k1; ++k) {
-        const int64_t at = (int64_t)k * s.ns + u.i;
-        take(k, s.pix[at], WITH_B ? v[at] : 0.0);
-    }
-    return m;
-}
-
-__device__ __forceinline__ int class_of(int m, int K, bool failed)
-{
-    return m == 0 ? pp::kEmpty : m < K ? pp::kFew : failed ? pp::kPivot : pp::kFitted;
-}
-
-// steps 1 and 2 of a unit: its class, and c when it is fitted
-template <int K>
-__device__ __forceinline__ int fit_unit(const Shape &s, const Unit &u, const double *v, double tau, double (&c)[K])
-{
-    double G[pp::packed(K)];
-    const int m = gram<K, true>(s, u, v, G, c);
-    if (m < K) return class_of(m, K, false);
-    if (fit::factor(KConst<K>{}, G, tau)) return pp::kPivot;
-    fit::solve(KConst<K>{}, G, c);
-    return pp::kFitted;
-}
-
-// v and out are not __restrict__: they may be the same array
+// the bodies, and why v and out are not __restrict__: cm2_modefit.h
 template <int K>
 __global__ __launch_bounds__(pp::kThreads) void k_pca_apply(Shape s, double tau, const double *v, double *out)
 {
-    const Unit u = my_unit<K>(s);
-    if (u.i < 0) return;
-    double c[K];
-    const int cls = fit_unit<K>(s, u, v, tau, c);
-    if (cls != pp::kFitted) {
-        for (int k = u.k0; k < u.k1; ++k) out[(int64_t)k * s.ns + u.i] = 0.0;
-        return;
-    }
-    auto residual = [&](int k, int32_t px, double x) {
-        double o = 0.0;
-        if (px >= 0) {
-            const double *__restrict__ ph = u.phi + (int64_t)k * K;
-            double p = c[0] * ph[0];
-#pragma unroll
-            for (int j = 1; j < K; ++j) p += c[j] * ph[j];
-            o = x - p;
-        }
-        return o;
-    };
-    int k = u.k0;
-    for (; k + kAhead<K> <= u.k1; k += kAhead<K>) {
-        int32_t px[kAhead<K>];
-        double x[kAhead<K>];
-#pragma unroll
-        for (int j = 0; j < kAhead<K>; ++j) {
-            const int64_t at = (int64_t)(k + j) * s.ns + u.i;
-            px[j] = s.pix[at];
-            x[j] = v[at];
-        }
-#pragma unroll
-        for (int j = 0; j < kAhead<K>; ++j) out[(int64_t)(k + j) * s.ns + u.i] = residual(k + j, px[j], x[j]);
-    }
-    for (; k < u.k1; ++k) {
-        const int64_t at = (int64_t)k * s.ns + u.i;
-        out[at] = residual(k, s.pix[at], v[at]);
-    }
+    mf::apply<K>(my_unit<K>(s), tau, v, out);
 }
 
-// coeff[(g K + j) ns + i] = c_j of unit (g, i), 0 for a skipped unit
 template <int K>
 __global__ __launch_bounds__(pp::kThreads) void k_pca_fit(Shape s, double tau, const double *__restrict__ v,
                                                            double *__restrict__ coeff)
 {
-    const Unit u = my_unit<K>(s);
-    if (u.i < 0) return;
-    double c[K];
-    const int cls = fit_unit<K>(s, u, v, tau, c);
-#pragma unroll
-    for (int j = 0; j < K; ++j) coeff[(u.g * K + j) * s.ns + u.i] = cls == pp::kFitted ? c[j] : 0.0;
+    mf::coefficients<K>(my_unit<K>(s), tau, v, coeff);
 }
 
-// status[g ns + i] = the class of unit (g, i); counts[0..3] += the units of each class (integer atomics: LDS first,
-// then one per class and workgroup)
 template <int K>
 __global__ __launch_bounds__(pp::kThreads) void k_pca_class(Shape s, double tau, uint8_t *__restrict__ status,
                                                              unsigned long long *__restrict__ counts)
 {
-    __shared__ unsigned int tally[4];
-    if (threadIdx.x < 4) tally[threadIdx.x] = 0u;
-    __syncthreads();
-    const Unit u = my_unit<K>(s);
-    if (u.i >= 0) {
-        double G[pp::packed(K)], unused[K];
-        const int m = gram<K, false>(s, u, nullptr, G, unused);
-        const bool failed = m >= K ? fit::factor(KConst<K>{}, G, tau) : false;
-        const int cls = class_of(m, K, failed);
-        status[u.g * s.ns + u.i] = (uint8_t)cls;
-        atomicAdd(&tally[cls], 1u);
-    }
-    __syncthreads();
-    if (threadIdx.x < 4 && tally[threadIdx.x]) atomicAdd(&counts[threadIdx.x], (unsigned long long)tally[threadIdx.x]);
+    mf::classify<K>([&] { return my_unit<K>(s); }, tau, status, counts);
 }
 
 }  // namespace
@@ -402,11 +278,9 @@ extern "C" int cm2_pca_create(cm2_pca **out, int64_t ns, int ndet, int ngroups, 
     CM2_CHECK(h_group_edges && h_chunk_edges && d_pix, "%s: null array", who);
     pp::Plan p;
     const pp::Status ps = pp::check(&p, ns, ndet, ngroups, h_group_edges, nchunks, h_chunk_edges, K);
-    CM2_CHECK(ps != pp::kBadK, "%s: K=%d outside [1, %d]", who, K, pp::kMaxK);
+    if (int rc = mf::check_create_status(who, ps, ndet, ngroups, K)) return rc;
     CM2_CHECK(ps != pp::kBadSize, "%s: ns=%lld, ndet=%d, ngroups=%d, nchunks=%lld must all be >= 1", who,
               (long long)ns, ndet, ngroups, (long long)nchunks);
-    CM2_CHECK(ps != pp::kBadEdges, "%s: the %d group edges must ascend strictly from 0 to ndet=%d", who, ngroups + 1,
-              ndet);
     CM2_CHECK(ps != pp::kBadChunks, "%s: the %lld chunk edges must ascend strictly from 0 to ns=%lld", who,
               (long long)nchunks + 1, (long long)ns);
     CM2_CHECK(ps == pp::kOk, "%s: ns=%lld x ndet=%d in %d groups and %lld chunks overflows the index types or a grid",
@@ -474,16 +348,11 @@ extern "C" int cm2_pca_set_modes(cm2_pca *h, const double *d_modes, void *stream
     hipStream_t st = as_stream(stream);
     CM2_HIP(hipMemcpyAsync(h->d_modes, d_modes, sizeof(double) * (size_t)(h->nchunks * h->ndet * h->K),
                            hipMemcpyDeviceToDevice, st));
-    CM2_HIP(hipMemsetAsync(h->d_counts, 0, 4 * sizeof(unsigned long long), st));
-    dispatch_int<1, pp::kMaxK>(h->K, [&](auto K) {
+    auto launch_class = [&](auto K) {
         k_pca_class<K><<<dim3((unsigned)h->plan.blocks), pp::kThreads, 0, st>>>(h->shape(), CM2_PCA_TAU, h->d_status,
                                                                                 h->d_counts);
-    });
-    CM2_LAUNCH_OK();
-    unsigned long long got[4];
-    CM2_HIP(cm2::download(got, h->d_counts, sizeof(got), st));
-    CM2_HIP(hipStreamSynchronize(st));
-    for (int c = 0; c < 4; ++c) h->nclass[c] = (int64_t)got[c];
+    };
+    if (int rc = mf::count_classes(h->K, launch_class, h->d_counts, st, h->nclass)) return rc;
     h->modes_set = true;
     return 0;
 }
@@ -493,8 +362,7 @@ extern "C" int cm2_pca_apply(cm2_pca *h, const double *d_in, double *d_out, void
     CM2_CHECK(h, "cm2_pca_apply: null handle");
     CM2_CHECK(d_in && d_out, "cm2_pca_apply: null vector");
     CM2_CHECK(h->modes_set, "cm2_pca_apply: no modes are set (cm2_pca_set_modes)");
-    CM2_CHECK(pp::apply_ok((uint64_t)reinterpret_cast<uintptr_t>(d_in), (uint64_t)reinterpret_cast<uintptr_t>(d_out),
-                           h->plan.nt),
+    CM2_CHECK(mf::apply_ok(d_in, d_out, h->plan.nt),
               "cm2_pca_apply: the output must be the input itself or not overlap it");
     dispatch_int<1, pp::kMaxK>(h->K, [&](auto K) {
         k_pca_apply<K><<<dim3((unsigned)h->plan.blocks), pp::kThreads, 0, as_stream(stream)>>>(h->shape(), CM2_PCA_TAU,
@@ -523,7 +391,5 @@ extern "C" int cm2_pca_status(const cm2_pca *h, uint8_t *d_status)
 {
     CM2_CHECK(h && d_status, "cm2_pca_status: null argument");
     CM2_CHECK(h->modes_set, "cm2_pca_status: no modes are set (cm2_pca_set_modes)");
-    CM2_HIP(hipMemcpyAsync(d_status, h->d_status, (size_t)h->plan.units, hipMemcpyDeviceToDevice, nullptr));
-    CM2_HIP(hipStreamSynchronize(nullptr));
-    return 0;
+    return mf::copy_status(d_status, h->d_status, h->plan.units);
 }

@@ -19,13 +19,19 @@
 #include <cstdint>
 #include <vector>
 
-#include "cm2_fit.h"
+#include "cm2_modefit_policy.h"
 
 namespace cm2 {
 namespace pca {
 
-constexpr int kThreads = 256;              // threads of every workgroup here (four waves)
-constexpr int kMaxK = 10;                  // modes per chunk
+// the workgroup (of every kernel here), the largest K, the classes of a unit and apply_ok: shared with cm2_cmode
+using modefit::kThreads;
+using modefit::kMaxK;
+using modefit::Class, modefit::kFitted, modefit::kEmpty, modefit::kFew, modefit::kPivot;
+using modefit::packed;
+using modefit::packed_at;
+using modefit::apply_ok;
+
 constexpr int kMfma = 16;                  // rows and columns of one v_mfma_f64_16x16x4_f64 result
 constexpr int kMfmaK = 4;                  // samples one instruction contracts
 constexpr int kTile = 128;                 // rows and columns of a workgroup tile: 2 x 2 waves of 64 x 64
@@ -34,12 +40,10 @@ constexpr int kStep = 16;                  // samples staged in LDS at a time
 constexpr int kPitch = 18;                 // doubles between the rows of a staged slab (kStep + 2)
 constexpr int kSegment = 4096;             // samples of a segment
 
-enum Class { kFitted = 0, kEmpty = 1, kFew = 2, kPivot = 3 };
-
 enum Status { kOk = 0, kBadK = 1, kBadSize = 2, kBadEdges = 3, kBadChunks = 4, kTooLarge = 5 };
 
-using fit::packed;
-using fit::packed_at;
+static_assert(kBadK == (int)modefit::kBadK && kBadSize == (int)modefit::kBadSize &&
+                  kBadEdges == (int)modefit::kBadEdges, "the shared refusals keep their codes");
 
 // LDS of a covariance workgroup: two staged slabs (row tile, column tile) of kTile rows
 constexpr size_t lds_bytes() { return (size_t)2 * kTile * kPitch * sizeof(double); }
@@ -98,13 +102,14 @@ constexpr bool modes_allowed(int64_t min_group, int K) { return min_group >= (in
 inline Status check(Plan *p, int64_t ns, int64_t ndet, int64_t ngroups, const int64_t *gedges, int64_t nchunks,
                     const int64_t *cedges, int K)
 {
-    if (K < 1 || K > kMaxK) return kBadK;
-    if (ns < 1 || ndet < 1 || ngroups < 1 || nchunks < 1 || !gedges || !cedges) return kBadSize;
-    if (!fit::edges_ok(gedges, ngroups, ndet)) return kBadEdges;
+    // the shared refusals in their places: a chunk count below 1 is a size, bad chunk edges come before the limits
+    const modefit::Status shared = modefit::check(ns, ndet, ngroups, gedges, K);
+    if (shared == modefit::kBadK) return kBadK;
+    if (shared == modefit::kBadSize || nchunks < 1 || !cedges) return kBadSize;
+    if (shared == modefit::kBadEdges) return kBadEdges;
     if (!fit::edges_ok(cedges, nchunks, ns)) return kBadChunks;
+    if (shared != modefit::kOk) return kTooLarge;
     const int64_t lim = (int64_t)1 << 31;
-    if (ndet >= lim) return kTooLarge;
-    if (ndet > (((int64_t)1 << 46) / ns)) return kTooLarge;
     // ndet <= 2^23 keeps sum n^2 <= ndet^2 below 2^46; nchunks times that and the items stay below 2^62
     if (ndet > ((int64_t)1 << 23) || nchunks > ((int64_t)1 << 16)) return kTooLarge;
     int64_t per_chunk = 0, pairs = 0, part = 0, smallest = ndet;
@@ -185,14 +190,6 @@ inline void slab_table(int64_t nchunks, const int64_t *cedges, std::vector<Slab>
             slabs->push_back(Slab{i, (int32_t)(left < kThreads ? left : kThreads), (int32_t)c});
         }
 }
-
-// do the doubles a[0, na) and b[0, nb) share a byte?  (addresses as integers: no GPU header here)
-inline bool overlap(uint64_t a, int64_t na, uint64_t b, int64_t nb)
-{
-    return a < b + (uint64_t)nb * sizeof(double) && b < a + (uint64_t)na * sizeof(double);
-}
-// apply: the output is the input itself or shares nothing with it
-inline bool apply_ok(uint64_t in, uint64_t out, int64_t nt) { return in == out || !overlap(in, nt, out, nt); }
 
 }  // namespace pca
 }  // namespace cm2

@@ -1340,7 +1340,41 @@ def focalplane_modes(xy, order, groups=None):
     return np.ascontiguousarray(np.stack(cols, axis=1))
 
 
-class CommonModeFilterLO(_TimeFilter):
+class _ModeFitFilter(_TimeFilter):
+    """Base of the filters that fit ``K`` modes per (group of detectors, time sample) unit through one library
+    family ``cm2_<_PREFIX>_*``: the stream's length, the coefficients, the classes of the units and the info
+    record, whose first entries ``_INFO`` names and whose last four count the units of each of ``CLASSES``."""
+    CLASSES = ("fitted", "empty", "few", "pivot")
+    _PREFIX = _INFO = None
+
+    def _set_length(self, pix_samples):
+        n = _size(pix_samples)
+        if n < self.ndet or n % self.ndet:
+            raise lp.ShapeError("pix_samples has %d entries, not a positive multiple of ndet = %d" % (n, self.ndet))
+        self.n, self.ns = n, n // self.ndet
+
+    def filter_info(self):
+        info = (ctypes.c_int64 * (len(self._INFO) + 4))()
+        _hip.call("cm2_%s_info" % self._PREFIX, self._handle.h, info)
+        return dict(zip(self._INFO + self.CLASSES, [int(v) for v in info]))
+
+    def coefficients(self, d):
+        """The fitted coefficients ``[ngroups, K, ns]`` of ``d`` (zeros for a skipped unit): the time streams of
+        the modes; nothing is subtracted."""
+        x = self._input(d)
+        out = D.empty(self.ngroups * self.K * self.ns)
+        _hip.call("cm2_%s_fit" % self._PREFIX, self._handle.h, D.ptr(x), D.ptr(out), D.stream())
+        return D.like_input(out, d).reshape(self.ngroups, self.K, self.ns)
+
+    def status(self):
+        """The class of every unit, ``[ngroups, ns]`` uint8 on the host: 0 fitted, 1 empty (no unflagged
+        detector), 2 few (fewer than ``K``), 3 pivot (collinear modes)."""
+        out = D.empty(self.ngroups * self.ns, torch.uint8)
+        _hip.call("cm2_%s_status" % self._PREFIX, self._handle.h, D.ptr(out))
+        return D.to_host(out).reshape(self.ngroups, self.ns)
+
+
+class CommonModeFilterLO(_ModeFitFilter):
     """
     Common-mode filter: per group of detectors and time sample, fit ``K`` templates ``Phi[k, :]`` across the
     unflagged detectors and subtract them (``M - M Phi G^-1 Phi^T M``, symmetric and idempotent;
@@ -1355,8 +1389,7 @@ class CommonModeFilterLO(_TimeFilter):
     coefficients are 0; ``filter_info()`` counts them and ``status()`` names them.  Flagged samples are 0 in the
     output.
     """
-    CLASSES = ("fitted", "empty", "few", "pivot")
-    _ENTRY = "cm2_cmode_apply"
+    _ENTRY, _PREFIX, _INFO = "cm2_cmode_apply", "cmode", ("ns", "ndet", "ngroups", "K")
 
     def __init__(self, pix_samples, ndet, modes=None, groups=None):
         self.edges = cmode_groups(ndet, groups)
@@ -1369,10 +1402,7 @@ class CommonModeFilterLO(_TimeFilter):
         if not 1 <= shape[1] <= CMODE_MAX_K:
             raise ValueError("modes has K = %d templates, K must be in [1, %d]" % (shape[1], CMODE_MAX_K))
         self.K = int(shape[1])
-        n = _size(pix_samples)
-        if n < self.ndet or n % self.ndet:
-            raise lp.ShapeError("pix_samples has %d entries, not a positive multiple of ndet = %d" % (n, self.ndet))
-        self.n, self.ns = n, n // self.ndet
+        self._set_length(pix_samples)
         D.require_gpu()
         self._d_pix = D.i32(pix_samples).reshape(-1)
         d_modes = D.f64(modes).reshape(-1)
@@ -1381,26 +1411,6 @@ class CommonModeFilterLO(_TimeFilter):
                   self.edges.ctypes.data_as(_I64P), self.K, D.ptr(d_modes), D.ptr(self._d_pix), D.stream())
         self._handle = _hip.Handle("cm2_cmode_destroy", handle, keep=self._d_pix)
         super(CommonModeFilterLO, self).__init__(nargin=self.n, nargout=self.n, matvec=self.mult, symmetric=True)
-
-    def filter_info(self):
-        info = (ctypes.c_int64 * 8)()
-        _hip.call("cm2_cmode_info", self._handle.h, info)
-        return dict(zip(("ns", "ndet", "ngroups", "K") + self.CLASSES, [int(v) for v in info]))
-
-    def coefficients(self, d):
-        """The fitted coefficients ``[ngroups, K, ns]`` of ``d`` (zeros for a skipped unit); nothing is
-        subtracted."""
-        x = self._input(d)
-        out = D.empty(self.ngroups * self.K * self.ns)
-        _hip.call("cm2_cmode_fit", self._handle.h, D.ptr(x), D.ptr(out), D.stream())
-        return D.like_input(out, d).reshape(self.ngroups, self.K, self.ns)
-
-    def status(self):
-        """The class of every unit, ``[ngroups, ns]`` uint8 on the host: 0 fitted, 1 empty (no unflagged
-        detector), 2 few (fewer than ``K``), 3 pivot (collinear templates)."""
-        out = D.empty(self.ngroups * self.ns, torch.uint8)
-        _hip.call("cm2_cmode_status", self._handle.h, D.ptr(out))
-        return D.to_host(out).reshape(self.ngroups, self.ns)
 
 
 # ================================================================= PCAFilterLO ===
@@ -1418,7 +1428,7 @@ def pca_select_modes(cov, K):
     return np.ascontiguousarray(v * sign), np.ascontiguousarray(w)
 
 
-class PCAFilterLO(_TimeFilter):
+class PCAFilterLO(_ModeFitFilter):
     """
     PCA filter: per group of detectors and time sample, fit ``K`` modes ``Phi_c[k, :]`` across the unflagged
     detectors and subtract them, with modes that differ from chunk to chunk and are learnt from the data: the leading
@@ -1441,8 +1451,8 @@ class PCAFilterLO(_TimeFilter):
     flags.  A unit (group x sample) with fewer than ``K`` unflagged detectors, or whose modes are collinear on them,
     is skipped as in :class:`CommonModeFilterLO`.
     """
-    CLASSES = ("fitted", "empty", "few", "pivot")
-    _ENTRY = "cm2_pca_apply"
+    _ENTRY, _PREFIX = "cm2_pca_apply", "pca"
+    _INFO = ("ns", "ndet", "ngroups", "nchunks", "K", "cov_doubles", "work_doubles", "work_items", "modes_set")
 
     def __init__(self, pix_samples, ndet, nmodes=1, groups=None, chunks=None, modes=None):
         self.edges = cmode_groups(ndet, groups)
@@ -1450,10 +1460,7 @@ class PCAFilterLO(_TimeFilter):
         if int(nmodes) != nmodes or not 1 <= int(nmodes) <= PCA_MAX_K:
             raise ValueError("nmodes must be an integer in [1, %d], got %r" % (PCA_MAX_K, nmodes))
         self.K = int(nmodes)
-        n = _size(pix_samples)
-        if n < self.ndet or n % self.ndet:
-            raise lp.ShapeError("pix_samples has %d entries, not a positive multiple of ndet = %d" % (n, self.ndet))
-        self.n, self.ns = n, n // self.ndet
+        self._set_length(pix_samples)
         self.chunk_edges = hwpss_plan(self.ns, chunks)
         self.nchunks = int(self.chunk_edges.size) - 1
         if modes is not None:
@@ -1543,23 +1550,3 @@ class PCAFilterLO(_TimeFilter):
         self.eigenvalues = eig
         self.set_modes(modes)
         return self
-
-    def filter_info(self):
-        info = (ctypes.c_int64 * 13)()
-        _hip.call("cm2_pca_info", self._handle.h, info)
-        names = ("ns", "ndet", "ngroups", "nchunks", "K", "cov_doubles", "work_doubles", "work_items", "modes_set")
-        return dict(zip(names + self.CLASSES, [int(v) for v in info]))
-
-    def coefficients(self, d):
-        """The fitted coefficients ``[ngroups, K, ns]`` of ``d`` (zeros for a skipped unit): the mode time streams;
-        nothing is subtracted."""
-        x = self._input(d)
-        out = D.empty(self.ngroups * self.K * self.ns)
-        _hip.call("cm2_pca_fit", self._handle.h, D.ptr(x), D.ptr(out), D.stream())
-        return D.like_input(out, d).reshape(self.ngroups, self.K, self.ns)
-
-    def status(self):
-        """The class of every unit, ``[ngroups, ns]`` uint8 on the host: 0 fitted, 1 empty, 2 few, 3 pivot."""
-        out = D.empty(self.ngroups * self.ns, torch.uint8)
-        _hip.call("cm2_pca_status", self._handle.h, D.ptr(out))
-        return D.to_host(out).reshape(self.ngroups, self.ns)

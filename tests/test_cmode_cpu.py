@@ -42,10 +42,12 @@ def test_names_are_exported_and_the_header_declares_the_entry_points():
         assert any(re.search(p, k) for p in KR.NO_SPILL), k
     from cosmomap2_amd import build as B
     assert "cm2_cmode.hip" not in B.FMA_OK
-    src = open(os.path.join(CSRC, "cm2_cmode.hip")).read()
+    hip, unit = (open(os.path.join(CSRC, f)).read() for f in ("cm2_cmode.hip", "cm2_modefit.h"))        # with the unit
+    src = hip + unit
     atomics = re.findall(r"\batomic\w*\s*\(\s*&?\s*(\w+)", src)                # integer tallies only
     assert sorted(atomics) == ["counts", "tally"] and re.search(r"unsigned long long \*__restrict__ counts", src)
-    assert "shfl" not in src.split('#include "cm2_common.h"')[1]               # no cross-lane sums
+    assert "shfl" not in hip.split('#include "cm2_modefit.h"')[1]                # no cross-lane sums: the file's code
+    assert "shfl" not in unit.split('#include "cm2_common.h"')[1]               # and the unit's
 
 
 # ---------------------------------------------------------------- cmode_groups ----

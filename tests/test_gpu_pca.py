@@ -334,6 +334,54 @@ def test_the_modes_of_every_chunk_are_annihilated(cm, K):
         assert C.excess(out, np.zeros(cs.nt), r.S, c) <= 1.0
 
 
+# ------------------------------------------- 2b: one unit, two filters, the same bits ----
+# The PCA filter and the common-mode filter run the same unit (cm2_modefit.h): the same operations in the same order,
+# no contraction, IEEE division and square root.  So where they are given the same detectors, flags, modes and data
+# they agree bit for bit, NaNs included -- not within a bound.
+def both_filters(F, Fc, v):
+    return (F * v, Fc * v), (F.coefficients(v), Fc.coefficients(v)), (F.status(), Fc.status())
+
+
+@pytest.mark.parametrize("K", [1, 3, 6, 10])
+def test_one_chunk_is_the_common_mode_filter_bit_for_bit(cm, K):
+    cs = C.case(APPLY_CASES[K])
+    assert cs.K == K and cs.ns == C.NS == 773
+    for pattern in C.PATTERNS:
+        d = C.data(APPLY_CASES[K], pattern)
+        F = cm.I.PCAFilterLO(d.pix, cs.ndet, groups=cs.edges, chunks=None, modes=cs.modes[None])
+        Fc = cm.I.CommonModeFilterLO(d.pix, cs.ndet, modes=cs.modes, groups=cs.edges)
+        assert F.nchunks == 1 and F.K == Fc.K == K
+        out, cf, st = both_filters(F, Fc, d.v)
+        assert same_bits(*out), pattern
+        assert same_bits(*cf) and cf[0].shape == (len(cs.sizes), K, cs.ns), pattern
+        assert np.array_equal(*st) and st[0].dtype == np.uint8, pattern
+        info, info_c = F.filter_info(), Fc.filter_info()
+        assert [info[k] for k in F.CLASSES] == [info_c[k] for k in Fc.CLASSES], pattern
+        assert sum(info[k] for k in F.CLASSES) == len(cs.sizes) * cs.ns
+        assert np.isnan(out[0]).any() == (pattern == "nan")
+
+
+@pytest.mark.parametrize("K", [1, 3, 6, 10])
+def test_every_chunk_is_a_common_mode_filter_on_its_columns(cm, K):
+    """chunks of 1, 254, 1, 1, 256 and 260 samples: a chunk of one sample, chunks that end one short of, on and one
+    past the 256-thread slab, and a last chunk that is no multiple of 256"""
+    cs, modes = C.case(APPLY_CASES[K]), apply_modes(K)
+    assert APPLY_CEDGES.tolist() == [0, 1, 255, 256, 257, 513, 773] and cs.ndet >= K + 1
+    for pattern in C.PATTERNS:
+        d = C.data(APPLY_CASES[K], pattern)
+        F = apply_op(cm, K, pattern)
+        out, cf, st = F * d.v, F.coefficients(d.v), F.status()
+        pix2, v2 = d.pix.reshape(cs.ndet, cs.ns), d.v.reshape(cs.ndet, cs.ns)
+        for c, (a, b) in enumerate(zip(APPLY_CEDGES[:-1], APPLY_CEDGES[1:])):
+            Fc = cm.I.CommonModeFilterLO(np.ascontiguousarray(pix2[:, a:b]).reshape(-1), cs.ndet, modes=modes[c],
+                                         groups=cs.edges)
+            vc = np.ascontiguousarray(v2[:, a:b]).reshape(-1)
+            what = (pattern, c)
+            assert same_bits(out.reshape(cs.ndet, cs.ns)[:, a:b], (Fc * vc).reshape(cs.ndet, b - a)), what
+            assert same_bits(cf[:, :, a:b], Fc.coefficients(vc)), what
+            assert np.array_equal(st[:, a:b], Fc.status()), what
+
+
 # ---------------------------------------------------------------------- 3: chain ----
 def test_learn_then_apply_and_the_quality_case(cm):
     q, host = R.quality(), R.quality_on_the_host()

@@ -47,10 +47,12 @@ def test_names_are_exported_and_the_header_declares_the_entry_points():
     for k in ("k_pca_cov", "k_pca_cov_final", "k_pca_apply<10>", "k_pca_fit<1>", "k_pca_class<6>"):
         assert any(re.search(p, k) for p in KR.NO_SPILL), k            # the build refuses spills in them
     assert "cm2_pca.hip" not in B.FMA_OK
-    src = open(os.path.join(CSRC, "cm2_pca.hip")).read()
-    atomics = re.findall(r"\batomic\w*\s*\(\s*&?\s*(\w+)", src)          # integer tallies only
+    hip, unit = (open(os.path.join(CSRC, f)).read() for f in ("cm2_pca.hip", "cm2_modefit.h"))        # with the unit
+    src = hip + unit
+    atomics = re.findall(r"\batomic\w*\s*\(\s*&?\s*(\w+)", src)                # integer tallies only
     assert sorted(atomics) == ["counts", "tally"] and re.search(r"unsigned long long \*__restrict__ counts", src)
-    assert "shfl" not in src.split('#include "cm2_common.h"')[1]         # no cross-lane sums
+    assert "shfl" not in hip.split('#include "cm2_modefit.h"')[1]                # no cross-lane sums: the file's code
+    assert "shfl" not in unit.split('#include "cm2_common.h"')[1]               # and the unit's
     assert not hasattr(L.PCAFilterLO, "_apply_tiles") and issubclass(L.PCAFilterLO, L._TimeFilter)
     assert "NOT linear in ``d``" in L.PCAFilterLO.__doc__ and "use_flags=False" in L.PCAFilterLO.__doc__
 
