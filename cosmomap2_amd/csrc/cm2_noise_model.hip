@@ -8,7 +8,7 @@
 //                            average='mean'): segments of L samples every L/2 inside each block (a tail
 //                            that does not fill a segment is ignored), periodic Hann window, one-sided
 //                            |X|^2 summed in segment order.
-//   cm2_noise_bands_from_psd PSD -> first row of an SPD inverse-noise band: S_k = P_k fs / m_k (S_0 := S_1),
+//   cm2_noise_bands_from_psd PSD -> first row of an SPD inverse-noise band: S of cm2_psd_bands.h,
 //                            G = 1/S, c_j = irfft(G, L)[j] as a fixed-order cosine sum, Bartlett taper
 //                            a_j = (1 - j/lambda) c_j.  The symbol of the band is G smoothed by the Fejer
 //                            kernel (>= 0), so every block is SPD by construction.
@@ -20,6 +20,7 @@
 // workspace cap; the last batch is padded with zero segments), so a segment's rocFFT transform is the same
 // whichever segments share its batch, and the per-bin sums run in segment order across batch boundaries:
 // a block estimated alone gives the bits of the same block estimated inside a group.
+#include "cm2_psd_bands.h"
 #include "cm2_rocfft.h"
 #include "cm2_stream_policy.h"
 
@@ -27,13 +28,11 @@
 #include <vector>
 
 using namespace cm2;
+using namespace cm2::psd;
 
 namespace {
 
-constexpr int64_t kMinL = 256, kMaxL = 65536;
 constexpr int64_t kBatchSamples = int64_t(1) << 24;     // segments per batch * L, at most (128 MB of input)
-
-bool pow2_in_range(int64_t L) { return L >= kMinL && L <= kMaxL && (L & (L - 1)) == 0; }
 
 // One workgroup per segment of the batch: gather the L samples of segment g = first + blockIdx.x, subtract
 // their mean (detrend = 1: every thread sums its samples j = t, t+256, ... in order, then the fixed tree of
@@ -96,46 +95,6 @@ __global__ __launch_bounds__(256) void k_psd_finish(const int64_t *__restrict__ 
     psd[i] = psd[i] * (m / ((double)(seg_off[b + 1] - seg_off[b]) * fs * wsum2));
 }
 
-// G[b][k] = 1 / S_k with S_k = P_k fs / m_k and S_0 := S_1.  The first (block, bin) whose S is not positive
-// and finite, or so small that 1 / S overflows, goes to *bad (flat index b * nfreq + k, the smallest one wins).
-__global__ __launch_bounds__(256) void k_bands_inverse(const double *__restrict__ psd, int64_t nb, int64_t nfreq,
-                                                        double fs, double *__restrict__ G,
-                                                        unsigned long long *__restrict__ bad)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nb * nfreq) return;
-    const int64_t b = i / nfreq, k = i - b * nfreq;
-    const int64_t kk = k == 0 ? 1 : k;
-    const double m = (kk == nfreq - 1) ? 1.0 : 2.0;
-    const double S = psd[b * nfreq + kk] * fs / m;
-    const double g = 1.0 / S;
-    if (!(S > 0.0) || !isfinite(S) || !isfinite(g)) atomicMin(bad, (unsigned long long)(b * nfreq + kk));
-    G[i] = g;
-}
-
-// G[b][k] = sqrt(S_k), same S.  Zero is allowed; the first (block, bin) whose S is negative or not finite
-// goes to *bad.
-__global__ __launch_bounds__(256) void k_bands_sqrt(const double *__restrict__ psd, int64_t nb, int64_t nfreq,
-                                                     double fs, double *__restrict__ G,
-                                                     unsigned long long *__restrict__ bad)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nb * nfreq) return;
-    const int64_t b = i / nfreq, k = i - b * nfreq;
-    const int64_t kk = k == 0 ? 1 : k;
-    const double m = (kk == nfreq - 1) ? 1.0 : 2.0;
-    const double S = psd[b * nfreq + kk] * fs / m;
-    if (!(S >= 0.0) || !isfinite(S)) atomicMin(bad, (unsigned long long)(b * nfreq + kk));
-    G[i] = sqrt(S);
-}
-
-// cos(2 pi m / L), m < L (2m/L is exact: L is a power of two)
-__global__ __launch_bounds__(256) void k_bands_cos_table(int64_t L, double *__restrict__ tab)
-{
-    const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (m < L) tab[m] = cospi((double)(2 * m) / (double)L);
-}
-
 // One thread per (block, lag j < lambda):
 //   c_j = (G_0 + (-1)^j G_{L/2} + 2 sum_{k=1}^{L/2-1} G_k cos(2 pi j k / L)) / L     (= numpy.fft.irfft(G, L)[j])
 //   a_j = (1 - j/lambda) c_j
@@ -148,9 +107,7 @@ __global__ __launch_bounds__(256) void k_bands_lags(const double *__restrict__ G
     const int64_t b = i / lambda, j = i - b * lambda;
     const int64_t nfreq = L / 2 + 1, mask = L - 1;
     const double *g = G + b * nfreq;
-    double acc = 0.0;
-    int64_t phase = j;                                   // j * k mod L
-    for (int64_t k = 1; k < nfreq - 1; ++k, phase = (phase + j) & mask) acc += g[k] * tab[phase];
+    const double acc = cos_sum([=](int64_t k) { return g[k]; }, tab, 1, nfreq - 1, j, j, mask);   // (j k) mod L
     const double nyq = (j & 1) ? -g[nfreq - 1] : g[nfreq - 1];
     const double c = (g[0] + nyq + 2.0 * acc) / (double)L;
     bands[i] = (1.0 - (double)j / (double)lambda) * c;
@@ -207,8 +164,7 @@ extern "C" int cm2_psd_create(cm2_psd **out, int64_t nperseg, int detrend, int64
 {
     CM2_CHECK(out, "cm2_psd_create: NULL argument");
     *out = nullptr;
-    CM2_CHECK(pow2_in_range(nperseg), "cm2_psd_create: nperseg=%lld is not a power of two in [256, 65536]",
-              (long long)nperseg);
+    CM2_CHECK_NPERSEG("cm2_psd_create", nperseg);
     CM2_CHECK(detrend == 0 || detrend == 1, "cm2_psd_create: detrend=%d (0 = none, 1 = constant)", detrend);
     if (max_work_bytes <= 0) max_work_bytes = int64_t(512) << 20;
     cm2_psd *p = new cm2_psd();
@@ -278,60 +234,36 @@ extern "C" int cm2_psd_welch(cm2_psd *p, const double *d_tod, const int64_t *h_s
     return 0;
 }
 
-// PSD -> band with G = 1/S (sqrt_mode 0) or G = sqrt(S) (1): the two entry points below
-static int bands_from_psd(const char *who, int sqrt_mode, const double *d_psd, int64_t nb, int64_t nperseg,
-                          double fsample, int64_t lambda, double *d_bands, void *stream_)
+// PSD -> band with G = 1/S (kInverse) or G = sqrt(S) (kSqrt): the two entry points below
+template <int G>
+static int bands_from_psd(const char *who, const double *d_psd, int64_t nb, int64_t nperseg, double fsample,
+                          int64_t lambda, double *d_bands, void *stream_)
 {
-    CM2_CHECK(d_psd && d_bands, "%s: NULL argument", who);
-    CM2_CHECK(nb >= 1, "%s: nb=%lld < 1", who, (long long)nb);
-    CM2_CHECK(pow2_in_range(nperseg), "%s: nperseg=%lld is not a power of two in [256, 65536]", who,
-              (long long)nperseg);
+    if (int rc = check_args(who, d_psd, d_bands, nb, nperseg, fsample)) return rc;
     CM2_CHECK(lambda >= 1 && lambda <= nperseg / 2, "%s: lambda=%lld outside [1, %lld]", who,
               (long long)lambda, (long long)(nperseg / 2));
-    CM2_CHECK(fsample > 0.0 && std::isfinite(fsample), "%s: fsample=%g is not positive", who, fsample);
     hipStream_t stream = as_stream(stream_);
     const int64_t L = nperseg, nfreq = L / 2 + 1;
-    DevTemp<double> G, tab;
-    DevTemp<unsigned long long> bad;
-    CM2_HIP(G.alloc(nb * nfreq));
+    DevTemp<double> Gk, tab;
+    CM2_HIP(Gk.alloc(nb * nfreq));
     CM2_HIP(tab.alloc(L));
-    CM2_HIP(bad.alloc(1));
-    CM2_HIP(hipMemsetAsync(bad, 0xFF, sizeof(unsigned long long), stream));
-    const unsigned grid = (unsigned)((nb * nfreq + kBlock - 1) / kBlock);
-    if (sqrt_mode)
-        k_bands_sqrt<<<grid, kBlock, 0, stream>>>(d_psd, nb, nfreq, fsample, G, bad);
-    else
-        k_bands_inverse<<<grid, kBlock, 0, stream>>>(d_psd, nb, nfreq, fsample, G, bad);
+    if (int rc = spectrum<G>(d_psd, nb, nfreq, fsample, Gk, stream)) return rc;
+    k_bands_cos_table<<<blocks_for(L), kBlock, 0, stream>>>(L, tab);
     CM2_LAUNCH_OK();
-    unsigned long long h_bad = 0;
-    CM2_HIP(cm2::read_back(&h_bad, bad, sizeof(h_bad), stream));
-    if (h_bad != ~0ULL) {
-        const long long b = (long long)(h_bad / (unsigned long long)nfreq), k = (long long)(h_bad % nfreq);
-        double v = 0.0;
-        CM2_HIP(cm2::read_back(&v, d_psd + h_bad, sizeof(v), stream));
-        if (sqrt_mode)
-            CM2_CHECK(false, "PSD of block %lld is negative or not finite at bin %lld (value %g): no colouring "
-                      "band can be built from it", b, k, v);
-        CM2_CHECK(false, "PSD of block %lld is not positive and finite at bin %lld (value %g): no inverse-noise "
-                  "band can be built from it", b, k, v);
-    }
-    k_bands_cos_table<<<(unsigned)((L + kBlock - 1) / kBlock), kBlock, 0, stream>>>(L, tab);
+    k_bands_lags<<<blocks_for(nb * lambda), kBlock, 0, stream>>>(Gk, tab, nb, L, lambda, d_bands);
     CM2_LAUNCH_OK();
-    k_bands_lags<<<(unsigned)((nb * lambda + kBlock - 1) / kBlock), kBlock, 0, stream>>>(G, tab, nb, L, lambda,
-                                                                                       d_bands);
-    CM2_LAUNCH_OK();
-    CM2_HIP(hipStreamSynchronize(stream));      // (G, tab go back to the cache on return)
+    CM2_HIP(hipStreamSynchronize(stream));      // (Gk, tab go back to the cache on return)
     return 0;
 }
 
 extern "C" int cm2_noise_bands_from_psd(const double *d_psd, int64_t nb, int64_t nperseg, double fsample,
                                         int64_t lambda, double *d_bands, void *stream_)
 {
-    return bands_from_psd("cm2_noise_bands_from_psd", 0, d_psd, nb, nperseg, fsample, lambda, d_bands, stream_);
+    return bands_from_psd<kInverse>("cm2_noise_bands_from_psd", d_psd, nb, nperseg, fsample, lambda, d_bands, stream_);
 }
 
 extern "C" int cm2_noise_filter_from_psd(const double *d_psd, int64_t nb, int64_t nperseg, double fsample,
                                          int64_t lambda, double *d_bands, void *stream_)
 {
-    return bands_from_psd("cm2_noise_filter_from_psd", 1, d_psd, nb, nperseg, fsample, lambda, d_bands, stream_);
+    return bands_from_psd<kSqrt>("cm2_noise_filter_from_psd", d_psd, nb, nperseg, fsample, lambda, d_bands, stream_);
 }

@@ -2,11 +2,11 @@
 // banded-Toeplitz prior C_a^-1 on the baseline offsets (interfaces/destriper.py solves with both).
 //
 // The third PSD -> band path beside cm2_noise_bands_from_psd (G = 1/S) and cm2_noise_filter_from_psd
-// (G = sqrt(S)) of cm2_noise_model.hip.  Per block, from one row P_k (k = 0 .. n/2, n = nperseg) of the Welch PSD,
-// with the baseline length L:
+// (G = sqrt(S)) of cm2_noise_model.hip; cm2_psd_bands.h has what the three share.  Per block, from one row P_k
+// (k = 0 .. n/2, n = nperseg) of the Welch PSD, with the baseline length L:
 //
-//   k_oprior_spectrum  S_k = P_k fs / m_k (m_k = 1 at k = 0 and n/2, else 2), S_0 := S_1; the first (block, bin)
-//                      whose S is not positive and finite is reported
+//   spectrum<kIdentity> S_k as cm2_psd_bands.h states it; the first (block, bin) whose S is not positive and finite
+//                      is refused
 //   k_oprior_white     sigma^2 = (4/n) sum_{k = n/4}^{n/2 - 1} S_k: the white level, when the caller gives none
 //   k_oprior_terms     W_k = m_k R_k D_k, R_k = max(S_k - sigma^2, 0) the correlated part,
 //                      D_k = sin^2(L w_k / 2) / (L^2 sin^2(w_k / 2)), w_k = 2 pi k / n, D_0 = 1: the transfer
@@ -21,43 +21,19 @@
 //   k_oprior_band      band_i = (1 - i/lambda) (1/M) sum_{k = 0}^{M/2} m'_k H_k cos(2 pi i k / M), i < lambda <= M/2
 //                      (m' like m, on M): the second Bartlett taper makes every block SPD.
 //
-// One thread per output, every sum in increasing index order in one accumulator, no atomics on doubles: a block
-// processed alone gives the bits of the same block processed inside a group.  The angles are reduced in
-// integers ((k L j) mod n, (k L) mod n, (i j) mod M) before cospi / sinpi see them.
-#include "cm2_common.h"
+// One thread per output, every sum in increasing index order in one accumulator (the cosine sums are cos_sum of
+// cm2_psd_bands.h), no atomics on doubles: a block processed alone gives the bits of the same block processed inside
+// a group.  The angles are reduced in integers ((k L j) mod n, (k L) mod n, (i j) mod M) before cospi / sinpi see
+// them.
+#include "cm2_psd_bands.h"
 
 #include <cmath>
 #include <vector>
 
 using namespace cm2;
+using namespace cm2::psd;
 
 namespace {
-
-constexpr int64_t kMinN = 256, kMaxN = 65536;
-
-bool pow2_in_range(int64_t n) { return n >= kMinN && n <= kMaxN && (n & (n - 1)) == 0; }
-
-// smallest power of two >= v (v >= 1)
-int64_t pow2_at_least(int64_t v)
-{
-    int64_t p = 1;
-    while (p < v) p <<= 1;
-    return p;
-}
-
-__global__ __launch_bounds__(256) void k_oprior_spectrum(const double *__restrict__ psd, int64_t nb, int64_t nfreq,
-                                                          double fs, double *__restrict__ S,
-                                                          unsigned long long *__restrict__ bad)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nb * nfreq) return;
-    const int64_t b = i / nfreq, k = i - b * nfreq;
-    const int64_t kk = k == 0 ? 1 : k;
-    const double m = (kk == nfreq - 1) ? 1.0 : 2.0;
-    const double s = psd[b * nfreq + kk] * fs / m;
-    if (!(s > 0.0) || !isfinite(s)) atomicMin(bad, (unsigned long long)(b * nfreq + kk));
-    S[i] = s;
-}
 
 // one thread per block: the upper half of the band, in increasing k
 __global__ __launch_bounds__(256) void k_oprior_white(const double *__restrict__ S, int64_t nb, int64_t n,
@@ -90,13 +66,6 @@ __global__ __launch_bounds__(256) void k_oprior_terms(const double *__restrict__
     W[i] = (m * (r > 0.0 ? r : 0.0)) * D;
 }
 
-// tab[m] = cos(2 pi m / N), m < N (2m/N is exact: N is a power of two)
-__global__ __launch_bounds__(256) void k_oprior_cos_table(int64_t N, double *__restrict__ tab)
-{
-    const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (m < N) tab[m] = cospi((double)(2 * m) / (double)N);
-}
-
 // one thread per (block, j < K)
 __global__ __launch_bounds__(256) void k_oprior_q(const double *__restrict__ W, const double *__restrict__ tab,
                                                    int64_t nb, int64_t n, int64_t L, int64_t K,
@@ -107,10 +76,7 @@ __global__ __launch_bounds__(256) void k_oprior_q(const double *__restrict__ W, 
     const int64_t b = i / K, j = i - b * K;
     const int64_t nfreq = n / 2 + 1, mask = n - 1;
     const double *w = W + b * nfreq;
-    const int64_t step = (L * j) & mask;
-    double acc = 0.0;
-    int64_t phase = 0;                                   // (k L j) mod n
-    for (int64_t k = 0; k < nfreq; ++k, phase = (phase + step) & mask) acc += w[k] * tab[phase];
+    const double acc = cos_sum([=](int64_t k) { return w[k]; }, tab, 0, nfreq, 0, (L * j) & mask, mask);
     qt[i] = (1.0 - (double)j / (double)K) * (acc / (double)n);
 }
 
@@ -125,9 +91,7 @@ __global__ __launch_bounds__(256) void k_oprior_invert(const double *__restrict_
     const int64_t b = t / nh, i = t - b * nh;
     const int64_t mask = M - 1;
     const double *q = qt + b * K;
-    double acc = 0.0;
-    int64_t phase = i;                                   // (i j) mod M
-    for (int64_t j = 1; j < K; ++j, phase = (phase + i) & mask) acc += q[j] * tab[phase];
+    const double acc = cos_sum([=](int64_t j) { return q[j]; }, tab, 1, K, i, i, mask);             // (i j) mod M
     const double Q = q[0] + 2.0 * acc;
     const double f = floor * sigma2[b] / (double)L;
     H[t] = 1.0 / (Q > f ? Q : f);
@@ -143,16 +107,10 @@ __global__ __launch_bounds__(256) void k_oprior_band(const double *__restrict__ 
     const int64_t b = t / lambda, i = t - b * lambda;
     const int64_t nh = M / 2 + 1, mask = M - 1;
     const double *h = H + b * nh;
-    double acc = 0.0;
-    int64_t phase = 0;                                   // (i k) mod M
-    for (int64_t k = 0; k < nh; ++k, phase = (phase + i) & mask) {
-        const double m = (k == 0 || k == nh - 1) ? 1.0 : 2.0;
-        acc += (m * h[k]) * tab[phase];
-    }
+    const auto term = [=](int64_t k) { return ((k == 0 || k == nh - 1) ? 1.0 : 2.0) * h[k]; };        // m'_k H_k
+    const double acc = cos_sum(term, tab, 0, nh, 0, i, mask);                                       // (i k) mod M
     bands[t] = (1.0 - (double)i / (double)lambda) * (acc / (double)M);
 }
-
-unsigned blocks_for(int64_t count) { return (unsigned)((count + kBlock - 1) / kBlock); }
 
 }  // namespace
 
@@ -161,21 +119,17 @@ extern "C" int cm2_offset_prior_from_psd(const double *d_psd, int64_t nb, int64_
                                          double floor, double *d_bands, double *h_sigma2_out, void *stream_)
 {
     const char *who = "cm2_offset_prior_from_psd";
-    CM2_CHECK(d_psd && d_bands, "%s: NULL argument", who);
-    CM2_CHECK(nb >= 1, "%s: nb=%lld < 1", who, (long long)nb);
-    CM2_CHECK(pow2_in_range(nperseg), "%s: nperseg=%lld is not a power of two in [256, 65536]", who,
-              (long long)nperseg);
-    CM2_CHECK(fsample > 0.0 && std::isfinite(fsample), "%s: fsample=%g is not positive", who, fsample);
+    if (int rc = check_args(who, d_psd, d_bands, nb, nperseg, fsample)) return rc;
     CM2_CHECK(baseline_length >= 1, "%s: baseline_length=%lld < 1", who, (long long)baseline_length);
     const int64_t n = nperseg, nfreq = n / 2 + 1, L = baseline_length;
     const int64_t K = nfreq / L;
     if (K < 2) {                                          // two baseline lags need n/2 + 1 >= 2L
-        const int64_t need = L <= kMaxN ? pow2_at_least(4 * L - 2) : 2 * kMaxN;
-        CM2_CHECK(need > kMaxN, "%s: nperseg=%lld holds %lld lag(s) of baselines of %lld samples, two are needed: "
+        const int64_t need = L <= kMaxL ? pow2_at_least(4 * L - 2) : 2 * kMaxL;
+        CM2_CHECK(need > kMaxL, "%s: nperseg=%lld holds %lld lag(s) of baselines of %lld samples, two are needed: "
                   "the smallest nperseg that would do is %lld", who, (long long)n, (long long)K, (long long)L,
                   (long long)need);
         CM2_CHECK(false, "%s: baselines of %lld samples are too long for any nperseg up to %lld (two lags need "
-                  "nperseg/2 + 1 >= 2 baseline_length)", who, (long long)L, (long long)kMaxN);
+                  "nperseg/2 + 1 >= 2 baseline_length)", who, (long long)L, (long long)kMaxL);
     }
     const int64_t M = pow2_at_least(2 * K), nh = M / 2 + 1;
     CM2_CHECK(lambda >= 1 && lambda <= M / 2, "%s: lambda=%lld outside [1, M/2 = %lld] (K = %lld baseline lags, "
@@ -187,7 +141,6 @@ extern "C" int cm2_offset_prior_from_psd(const double *d_psd, int64_t nb, int64_
                       "%s: sigma2 of block %lld is %g, not positive and finite", who, (long long)b, h_sigma2_in[b]);
     hipStream_t stream = as_stream(stream_);
     DevTemp<double> S, W, sigma2, tab_n, tab_m, qt, H;
-    DevTemp<unsigned long long> bad;
     CM2_HIP(S.alloc(nb * nfreq));
     CM2_HIP(W.alloc(nb * nfreq));
     CM2_HIP(sigma2.alloc(nb));
@@ -195,19 +148,7 @@ extern "C" int cm2_offset_prior_from_psd(const double *d_psd, int64_t nb, int64_
     CM2_HIP(tab_m.alloc(M));
     CM2_HIP(qt.alloc(nb * K));
     CM2_HIP(H.alloc(nb * nh));
-    CM2_HIP(bad.alloc(1));
-    CM2_HIP(hipMemsetAsync(bad, 0xFF, sizeof(unsigned long long), stream));
-    k_oprior_spectrum<<<blocks_for(nb * nfreq), kBlock, 0, stream>>>(d_psd, nb, nfreq, fsample, S, bad);
-    CM2_LAUNCH_OK();
-    unsigned long long h_bad = 0;
-    CM2_HIP(cm2::read_back(&h_bad, bad, sizeof(h_bad), stream));
-    if (h_bad != ~0ULL) {
-        const long long b = (long long)(h_bad / (unsigned long long)nfreq), k = (long long)(h_bad % nfreq);
-        double v = 0.0;
-        CM2_HIP(cm2::read_back(&v, d_psd + h_bad, sizeof(v), stream));
-        CM2_CHECK(false, "PSD of block %lld is not positive and finite at bin %lld (value %g): no offset prior can "
-                  "be built from it", b, k, v);
-    }
+    if (int rc = spectrum<kIdentity>(d_psd, nb, nfreq, fsample, S, stream)) return rc;
     std::vector<double> h_sigma2(nb);
     if (h_sigma2_in) {
         CM2_HIP(cm2::upload(sigma2, h_sigma2_in, sizeof(double) * nb, stream));
@@ -223,9 +164,9 @@ extern "C" int cm2_offset_prior_from_psd(const double *d_psd, int64_t nb, int64_
     }
     k_oprior_terms<<<blocks_for(nb * nfreq), kBlock, 0, stream>>>(S, sigma2, nb, n, L, W);
     CM2_LAUNCH_OK();
-    k_oprior_cos_table<<<blocks_for(n), kBlock, 0, stream>>>(n, tab_n);
+    k_bands_cos_table<<<blocks_for(n), kBlock, 0, stream>>>(n, tab_n);
     CM2_LAUNCH_OK();
-    k_oprior_cos_table<<<blocks_for(M), kBlock, 0, stream>>>(M, tab_m);
+    k_bands_cos_table<<<blocks_for(M), kBlock, 0, stream>>>(M, tab_m);
     CM2_LAUNCH_OK();
     k_oprior_q<<<blocks_for(nb * K), kBlock, 0, stream>>>(W, tab_n, nb, n, L, K, qt);
     CM2_LAUNCH_OK();

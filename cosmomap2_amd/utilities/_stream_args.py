@@ -52,6 +52,21 @@ def _check_nperseg(nperseg):
     return L
 
 
+def _check_fits_blocks(L, sizes):
+    if L > min(sizes):
+        raise ValueError("nperseg=%d is longer than the shortest block (%d samples)" % (L, min(sizes)))
+
+
+def _call_refusing_bins(name, *args):
+    """``_hip.call`` after the arguments were checked: an argument error is a bad bin, refused in the library's words"""
+    try:
+        _hip.call(name, *args)
+    except _hip.HipError as e:
+        if e.status == _hip.ERR_ARGUMENT:
+            raise ValueError(str(e)) from None
+        raise
+
+
 def _check_lam(lam, L):
     lam = _int("lam", lam)
     if not 1 <= lam <= L // 2:

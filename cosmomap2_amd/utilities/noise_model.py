@@ -24,8 +24,8 @@ import numpy as np
 
 from .. import _hip
 from .. import device as D
-from ._stream_args import (_MIN_L, _block_sizes, _check_detrend, _check_fsample, _check_lam, _check_nperseg,
-                           _check_psd, _int, _tod_length)
+from ._stream_args import (_MIN_L, _block_sizes, _call_refusing_bins, _check_detrend, _check_fits_blocks,
+                           _check_fsample, _check_lam, _check_nperseg, _check_psd, _int, _tod_length)
 
 __all__ = ["noise_psd", "inverse_noise_bands", "estimate_inverse_noise"]
 
@@ -60,8 +60,7 @@ def noise_psd(d, blocksize, nperseg, fsample=1.0, detrend="constant", work_bytes
     nt = _tod_length(d)
     sizes = _block_sizes(blocksize, nt)
     L = _check_nperseg(nperseg)
-    if L > min(sizes):
-        raise ValueError("nperseg=%d is longer than the shortest block (%d samples)" % (L, min(sizes)))
+    _check_fits_blocks(L, sizes)
     fs = _check_fsample(fsample)
     dt = _check_detrend(detrend)
     if work_bytes is not None and _int("work_bytes", work_bytes) <= 0:
@@ -82,6 +81,19 @@ def noise_psd(d, blocksize, nperseg, fsample=1.0, detrend="constant", work_bytes
     return f, D.to_host(psd)
 
 
+def _bands_from_psd(entry, psd, lam, fsample):
+    """The bands ``[nb, lam]`` that the library's ``entry`` builds from the PSD, on the side where the PSD is."""
+    nb, L = _check_psd(psd)
+    lam = _check_lam(lam, L)
+    fs = _check_fsample(fsample)
+    D.require_gpu()
+    p = D.f64(psd)
+    bands = D.empty(nb * lam)
+    _call_refusing_bins(entry, D.ptr(p), nb, L, fs, lam, D.ptr(bands), D.stream())
+    bands = bands.view(nb, lam)
+    return bands if D.is_dev(psd) else D.to_host(bands)
+
+
 def inverse_noise_bands(psd, lam, fsample=1.0):
     """
     First rows ``[nb, lam]`` of SPD banded-Toeplitz inverse-noise blocks from a one-sided PSD
@@ -96,20 +108,7 @@ def inverse_noise_bands(psd, lam, fsample=1.0):
     positive, finite and not so small that ``1/S`` overflows: any other bin raises ``ValueError``
     naming the block and the bin.
     """
-    nb, L = _check_psd(psd)
-    lam = _check_lam(lam, L)
-    fs = _check_fsample(fsample)
-    D.require_gpu()
-    p = D.f64(psd)
-    bands = D.empty(nb * lam)
-    try:
-        _hip.call("cm2_noise_bands_from_psd", D.ptr(p), nb, L, fs, lam, D.ptr(bands), D.stream())
-    except _hip.HipError as e:
-        if e.status == _hip.ERR_ARGUMENT:          # the arguments were checked above: a bad bin
-            raise ValueError(str(e)) from None
-        raise
-    bands = bands.view(nb, lam)
-    return bands if D.is_dev(psd) else D.to_host(bands)
+    return _bands_from_psd("cm2_noise_bands_from_psd", psd, lam, fsample)
 
 
 def estimate_inverse_noise(d, blocksize, lam, nperseg=None, fsample=1.0, detrend="constant", work_bytes=None):
@@ -128,8 +127,7 @@ def estimate_inverse_noise(d, blocksize, lam, nperseg=None, fsample=1.0, detrend
     _check_lam(lam, L)
     nt = _tod_length(d)
     sizes = _block_sizes(blocksize, nt)
-    if L > min(sizes):
-        raise ValueError("nperseg=%d is longer than the shortest block (%d samples)" % (L, min(sizes)))
+    _check_fits_blocks(L, sizes)
     _check_fsample(fsample)
     _check_detrend(detrend)
     _, psd = noise_psd(d, blocksize, L, fsample, detrend, work_bytes)

@@ -33,6 +33,7 @@ import numpy as np
 from .. import _hip
 from .. import device as D
 from ._stream_args import _block_sizes, _check_fsample, _check_lam, _check_psd, _int, _u64
+from .noise_model import _bands_from_psd
 
 __all__ = ["white_noise", "noise_filter_bands", "NoiseSimulator", "simulate_noise"]
 
@@ -80,20 +81,7 @@ def noise_filter_bands(psd, lam, fsample=1.0):
     to that resolution, not S itself -- the same limit the estimated inverse-noise band has.  ``P = 0`` is
     allowed; a negative or non-finite bin raises ``ValueError`` naming the block and the bin.
     """
-    nb, L = _check_psd(psd)
-    lam = _check_lam(lam, L)
-    fs = _check_fsample(fsample)
-    D.require_gpu()
-    p = D.f64(psd)
-    bands = D.empty(nb * lam)
-    try:
-        _hip.call("cm2_noise_filter_from_psd", D.ptr(p), nb, L, fs, lam, D.ptr(bands), D.stream())
-    except _hip.HipError as e:
-        if e.status == _hip.ERR_ARGUMENT:          # the arguments were checked above: a bad bin
-            raise ValueError(str(e)) from None
-        raise
-    bands = bands.view(nb, lam)
-    return bands if D.is_dev(psd) else D.to_host(bands)
+    return _bands_from_psd("cm2_noise_filter_from_psd", psd, lam, fsample)
 
 
 def _sim_sizes(blocksize):

@@ -32,10 +32,9 @@ import ctypes
 
 import numpy as np
 
-from .. import _hip
 from .. import device as D
-from ._stream_args import (_MAX_L, _MIN_L, _block_sizes, _check_detrend, _check_fsample, _check_nperseg, _check_psd,
-                           _int, _tod_length)
+from ._stream_args import (_MAX_L, _MIN_L, _block_sizes, _call_refusing_bins, _check_detrend, _check_fits_blocks,
+                           _check_fsample, _check_nperseg, _check_psd, _int, _tod_length)
 from .noise_model import noise_psd
 
 __all__ = ["offset_prior_bands", "estimate_offset_prior"]
@@ -145,14 +144,9 @@ def offset_prior_bands(psd, baseline_length, lam, fsample=1.0, sigma2=None, floo
     p = D.f64(psd)
     bands = D.empty(nb * lam)
     s_out = np.empty(nb, dtype=np.float64)
-    try:
-        _hip.call("cm2_offset_prior_from_psd", D.ptr(p), nb, n, fs, Lb, lam,
-                  None if s_in is None else s_in.ctypes.data_as(_DBLP), fl, D.ptr(bands),
-                  s_out.ctypes.data_as(_DBLP), D.stream())
-    except _hip.HipError as e:
-        if e.status == _hip.ERR_ARGUMENT:          # the arguments were checked above: a bad bin
-            raise ValueError(str(e)) from None
-        raise
+    _call_refusing_bins("cm2_offset_prior_from_psd", D.ptr(p), nb, n, fs, Lb, lam,
+                        None if s_in is None else s_in.ctypes.data_as(_DBLP), fl, D.ptr(bands),
+                        s_out.ctypes.data_as(_DBLP), D.stream())
     bands = bands.view(nb, lam)
     if D.is_dev(psd):
         return bands, D.f64(s_out)
@@ -180,8 +174,7 @@ def estimate_offset_prior(r, blocksize, baseline_length, lam=None, nperseg=None,
                              % (min(sizes), _MIN_L))
         nperseg = min(_MAX_L, 1 << (min(sizes).bit_length() - 1))
     n = _check_nperseg(nperseg)
-    if n > min(sizes):
-        raise ValueError("nperseg=%d is longer than the shortest block (%d samples)" % (n, min(sizes)))
+    _check_fits_blocks(n, sizes)
     K, M = _lags(n, Lb)
     per_block = [-(-s // Lb) for s in sizes]
     if lam is None:

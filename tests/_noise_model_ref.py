@@ -1,7 +1,8 @@
 """
 References, restatements and error bounds for the noise-model kernels (csrc/cm2_noise_model.hip): the Welch
 PSD per noise block (k_psd_pack, rocFFT, k_psd_accumulate, k_psd_finish) and the PSD -> band step
-(k_bands_inverse | k_bands_sqrt, k_bands_cos_table, k_bands_lags).
+(k_bands_spectrum<0> | k_bands_spectrum<1> and k_bands_cos_table of csrc/cm2_psd_bands.h, k_bands_lags around that
+header's cos_sum).
 
 Plain NumPy, no GPU, nothing of the package.
 
@@ -29,7 +30,7 @@ Plain NumPy, no GPU, nothing of the package.
         B_j = (1 - j/lam) (|G_0| + |G_{L/2}| + 2 sum_k |G_k|) / L.
 
     A band is accepted when |got - ref| <= C_LAG(L) 2^-53 B_j for every lag.  The constant is derived, not
-    measured.  k_bands_lags adds n = L/2 - 1 products g_k t_k serially in increasing k.  To first order, in
+    measured.  k_bands_lags adds n = L/2 - 1 products g_k t_k serially in increasing k (cos_sum).  To first order, in
     units of 2^-53 of |G_k| (|t| <= 1): G_k carries 2 (the product with fs and the division | square root;
     the division by m_k is exact), a table entry good to two ulps 4, the product 1, the serial sum at most
     n - 1 (its first term), the addition to G_0 + (-1)^j G_{L/2} 1 (the factor 2 and the division by L are
@@ -503,7 +504,7 @@ def _cos_table_f64(L):
 
 
 def bands_f64(psd, lam, fs, mode, mut=None):
-    """k_bands_inverse | k_bands_sqrt, k_bands_cos_table, k_bands_lags in float64 (the sum over k serial and
+    """k_bands_spectrum<0> | k_bands_spectrum<1>, k_bands_cos_table, k_bands_lags in float64 (the sum over k serial and
     increasing, as in the kernel)"""
     assert mut is None or mut in BAND_MUTATIONS, mut
     psd = np.atleast_2d(np.asarray(psd, dtype=np.float64))

@@ -1,6 +1,6 @@
 """
-The noise-model kernels (csrc/cm2_noise_model.hip) against the references of tests/_noise_model_ref.py, bin by
-bin and lag by lag, through the C entry points.
+The noise-model kernels (csrc/cm2_noise_model.hip, csrc/cm2_psd_bands.h) against the references of
+tests/_noise_model_ref.py, bin by bin and lag by lag, through the C entry points.
 
 Conventions of every case: the stream, the PSD and the bands are the middle of a larger buffer pre-filled with
 a sentinel whose bits must be unchanged after the call, and an output holds NaN before the call.  A PSD is
@@ -30,13 +30,13 @@ Kernels and the case that reaches them (to be kept in step with the code by hand
   k_psd_finish        fs = 1, 20; K_b = 1 .. 9          every PSD case
   exact zeros                                           test_constant_block_gives_exact_zeros; block 1 of the
                                                         L = 256 `impulses` (nothing but a tail impulse)
-  k_bands_inverse, k_bands_sqrt
+  k_bands_spectrum<0> (1/S), k_bands_spectrum<1> (sqrt(S)), spectrum_at
                       S_0 := S_1, bin 0 never read      test_bands_every_lag (bin 0 = NaN, -1, +inf)
                       m = 1 at the Nyquist bin          the one-bin PSD at k0 = 128
                       S = 0 under sqrt                  the one-bin PSDs; test_zero_psd_under_sqrt
                       the refusals, the smallest flat index
                                                         test_refusals, test_overflowing_inverse_is_refused
-  k_bands_cos_table, k_bands_lags
+  k_bands_cos_table, k_bands_lags (cos_sum)
                       3, 6, 21 threads; 384 (a second workgroup with a guarded remainder)
                                                         test_bands_every_lag[*-1 | 2 | 7 | 128]
                       every branch of the phase walk, the Nyquist sign, exact zeros where cos = 0

@@ -176,7 +176,7 @@ def test_abi_lists_name_the_new_entry_points():
     for name in ("cm2_noise_sim_draw", "cm2_noise_sim_destroy", "cm2_noise_sim_info"):
         assert name in _hip.PROTOTYPES
     assert "cm2_noise_sim_draw" not in _hip.RESTARTABLE          # add=True: a second run would add twice
-    for kernel in ("k_rng_fill<0>", "k_rng_fill<1>", "k_sim_interior", "k_bands_sqrt"):
+    for kernel in ("k_rng_fill<0>", "k_rng_fill<1>", "k_sim_interior", "cm2::psd::k_bands_spectrum<1>"):
         assert any(re.search(p, kernel) for p in KR.NO_SPILL), kernel
 
 
@@ -200,7 +200,7 @@ def test_library_cross_compiles_with_no_scratch_in_the_new_kernels():
         pytest.fail("hipcc not found at %s: the library cannot be built" % B.HIPCC)
     B.build(verbose=False)
     rows = {r["kernel"]: r for r in KR.load_all()}
-    for kernel in ("k_rng_fill<0>", "k_rng_fill<1>", "k_sim_interior", "k_bands_sqrt"):
+    for kernel in ("k_rng_fill<0>", "k_rng_fill<1>", "k_sim_interior", "cm2::psd::k_bands_spectrum<1>"):
         assert kernel in rows, sorted(rows)
         assert rows[kernel].get("scratch_bytes_per_lane", 0) == 0, rows[kernel]
         assert rows[kernel].get("vgpr_spill", 0) == 0, rows[kernel]

@@ -283,9 +283,10 @@ def test_abi_lists_name_the_new_entry_point():
     assert m and len(m.group(1).split(",")) == len(_hip.PROTOTYPES[name])
     assert m.group(1).startswith("const double *d_psd, int64_t nb, int64_t nperseg, double fsample,")
     assert re.search(r"#define CM2_ABI_VERSION 2\b", text)
-    src = open(os.path.join(ROOT, "cosmomap2_amd", "csrc", "cm2_offset_prior.hip")).read()
+    src = "".join(open(os.path.join(ROOT, "cosmomap2_amd", "csrc", f)).read()
+                  for f in ("cm2_offset_prior.hip", "cm2_psd_bands.h"))
     kernels = set(re.findall(r"\bvoid (k_\w+)\(", src))
-    assert {"k_oprior_spectrum", "k_oprior_q", "k_oprior_invert", "k_oprior_band"} <= kernels
+    assert {"k_bands_spectrum", "k_bands_cos_table", "k_oprior_q", "k_oprior_invert", "k_oprior_band"} <= kernels
     for kernel in kernels:
         assert any(re.search(p, kernel) for p in KR.NO_SPILL), kernel
     assert "atomicAdd" not in src
