@@ -192,6 +192,13 @@ PROTOTYPES = {
     "cm2_demod_info": [_vp, ctypes.POINTER(_i64)],
     "cm2_demod_run": [_vp, _vp, _vp, _vp, _vp, _int, _dbl, _vp, _vp, _vp, _vp, _vp, _vp],
     "cm2_demod_pick": [_vp, _vp, _vp, _int, _vp, _vp],
+    "cm2_template_create": [ctypes.POINTER(_vp), _i64, _int, _i64, ctypes.POINTER(_i64), _int, _vp, _int, _vp, _vp],
+    "cm2_template_destroy": [_vp],
+    "cm2_template_info": [_vp, ctypes.POINTER(_i64)],
+    "cm2_template_apply": [_vp, _vp, _vp, _vp],
+    "cm2_template_fit": [_vp, _vp, _vp, _vp],
+    "cm2_template_status": [_vp, _vp, _vp],
+    "cm2_template_tables": [_vp, _vp, _vp],
 }
 _RESTYPE = {"cm2_last_error": ctypes.c_char_p, "cm2_reduce_work_doubles": _i64,
             "cm2_gemm_tn_work_doubles": _i64, "cm2_pca_cov_doubles": _i64}
@@ -280,6 +287,7 @@ RESTARTABLE = frozenset([
     "cm2_jump_create", "cm2_jump_destroy", "cm2_jump_info", "cm2_jump_stat", "cm2_jump_scale", "cm2_jump_find",
     "cm2_pca_create", "cm2_pca_cov", "cm2_pca_set_modes", "cm2_pca_fit", "cm2_pca_status",
     "cm2_demod_create", "cm2_demod_destroy", "cm2_demod_info", "cm2_demod_run", "cm2_demod_pick",
+    "cm2_template_create", "cm2_template_apply", "cm2_template_fit", "cm2_template_status", "cm2_template_tables",
 ])
 
 

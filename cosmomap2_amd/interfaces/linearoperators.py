@@ -31,7 +31,7 @@ torch = D.torch
 __all__ = ["SparseLO", "ToeplitzLO", "BlockLO", "BlockDiagonalLO",
            "BlockDiagonalPreconditionerLO", "InverseLO", "CoarseLO", "DeflationLO",
            "TwoLevelPreconditionerLO", "FilterLO", "GroundFilterLO", "HWPSSFilterLO", "hwpss_plan",
-           "CommonModeFilterLO", "cmode_groups", "focalplane_modes", "PCAFilterLO", "pca_select_modes",
+           "TemplateFilterLO", "CommonModeFilterLO", "cmode_groups", "focalplane_modes", "PCAFilterLO", "pca_select_modes",
            "set_pointing_mode", "lp"]
 
 _I64P = ctypes.POINTER(ctypes.c_int64)
@@ -1295,6 +1295,98 @@ class HWPSSFilterLO(_TimeFilter):
         c, s = D.empty(self.ns), D.empty(self.ns)
         _hip.call("cm2_hwpss_tables", self._handle.h, D.ptr(c), D.ptr(s), D.stream())
         return c, s
+
+
+# ============================================================ TemplateFilterLO ===
+TEMPLATE_MAX_K = 16          # CM2_TEMPLATE_MAX_K of include/cosmomap2.h
+TEMPLATE_FITTED, TEMPLATE_FEW, TEMPLATE_PIVOT = 0, 1, 2      # CM2_TEMPLATE_FITTED, _FEW, _PIVOT
+
+
+class TemplateFilterLO(_TimeFilter):
+    """
+    Template filter: per detector and chunk, fit the caller's time-domain templates (a stage thermometer, the air
+    mass ``1 / sin(el)``, accelerometer or encoder channels, a scan-synchronous template sampled in time) to the
+    unflagged samples and subtract them (``M - M T G^-1 T^T M``, symmetric and idempotent; include/cosmomap2.h, f2i).
+    No counterpart in the reference.
+
+    ``TemplateFilterLO(templates, pix_samples, ndet=1, chunks=None, add_constant=True)``: ``templates[J, ns]`` (a 1-D
+    array is one template), shared by the detectors, a host array or an HBM tensor; it is copied, so it may go away.
+    ``pix_samples[ndet * ns]`` the pixel of every sample in the detector-major layout of ``expand_pointing`` (< 0 =
+    flagged; an HBM int32 tensor is adopted, not copied, and must not change afterwards); ``chunks`` as
+    :func:`hwpss_plan` takes them.  ``add_constant=True`` puts a constant in front of the templates (``K = J + 1``,
+    ``J = 0`` allowed: the constant alone) and subtracts from every template its mean over each chunk (all samples,
+    flagged or not), which does not change the output; coefficient 0 is then the offset at the chunk mean of the
+    templates, not at template value 0, and coefficient ``j`` belongs to ``templates[j - 1]``.
+    ``add_constant=False`` fits the templates as given (``K = J``).  ``1 <= K <= 16``.
+
+    A unit (detector x chunk) with fewer than ``K`` unflagged samples, or whose templates are collinear on them
+    (Cholesky pivot <= 2^-10 of its diagonal entry: two equal templates, a template that is constant on the chunk
+    beside the constant) or not finite on one of them, is skipped: its output and its coefficients are 0;
+    ``filter_info()`` counts them and ``status()`` names them.  Flagged samples are 0 in the output.
+    """
+    _ENTRY = "cm2_template_apply"
+
+    def __init__(self, templates, pix_samples, ndet=1, chunks=None, add_constant=True):
+        if not isinstance(add_constant, (bool, np.bool_)):
+            raise ValueError("add_constant must be True or False, not %r" % (add_constant,))
+        if int(ndet) != ndet or int(ndet) < 1:
+            raise ValueError("ndet must be a positive integer, got %r" % (ndet,))
+        self.add_constant, self.ndet = bool(add_constant), int(ndet)
+        if _dims(templates) not in (1, 2):
+            raise lp.ShapeError("templates must be a [J, ns] array (or one template of ns samples)")
+        shape = tuple(templates.shape) if hasattr(templates, "shape") else np.shape(templates)
+        self.J, self.ns = (1, int(shape[0])) if len(shape) == 1 else (int(shape[0]), int(shape[1]))
+        if self.ns < 1:
+            raise lp.ShapeError("templates must have at least one sample")
+        self.K = self.J + int(self.add_constant)
+        if not 1 <= self.K <= TEMPLATE_MAX_K:
+            raise ValueError("%d templates%s make K = %d, outside [1, %d]"
+                             % (self.J, " and the constant" if self.add_constant else "", self.K, TEMPLATE_MAX_K))
+        self.n = self.ndet * self.ns
+        if _size(pix_samples) != self.n:
+            raise lp.ShapeError("pix_samples has %d entries, expected ndet * ns = %d" % (_size(pix_samples), self.n))
+        self.edges = hwpss_plan(self.ns, chunks)
+        self.nchunks = int(self.edges.size) - 1
+        D.require_gpu()
+        self._d_pix = D.i32(pix_samples).reshape(-1)
+        d_tab = D.f64(templates).reshape(-1) if self.J else None
+        handle = ctypes.c_void_p()
+        _hip.call("cm2_template_create", ctypes.byref(handle), self.ns, self.ndet, self.nchunks,
+                  self.edges.ctypes.data_as(_I64P), self.J, D.ptr(d_tab) if self.J else None,
+                  int(self.add_constant), D.ptr(self._d_pix), D.stream())
+        self._handle = _hip.Handle("cm2_template_destroy", handle, keep=self._d_pix)
+        super(TemplateFilterLO, self).__init__(nargin=self.n, nargout=self.n, matvec=self.mult, symmetric=True)
+
+    def filter_info(self):
+        info = (ctypes.c_int64 * 10)()
+        _hip.call("cm2_template_info", self._handle.h, info)
+        return dict(zip(("ns", "ndet", "nchunks", "K", "add_constant", "fitted", "skipped_few", "skipped_pivot",
+                         "segment", "segments"), [int(v) for v in info]))
+
+    def coefficients(self, d):
+        """The fitted coefficients ``[ndet, nchunks, K]`` of ``d`` (zeros for a skipped unit); nothing is subtracted.
+        With the constant, ``[:, :, 0]`` is the offset at the chunk mean of the templates and ``[:, :, j]`` the
+        coefficient of ``templates[j - 1]``: ``coefficients(d)[:, :, 1]`` of an elevation nod fitted with the air
+        mass is the relative gain of every detector."""
+        x = self._input(d)
+        out = D.empty(self.ndet * self.nchunks * self.K)
+        _hip.call("cm2_template_fit", self._handle.h, D.ptr(x), D.ptr(out), D.stream())
+        return D.like_input(out, d).reshape(self.ndet, self.nchunks, self.K)
+
+    def status(self):
+        """The class of every unit, ``[ndet, nchunks]`` uint8 on the host: 0 fitted, 1 skipped for fewer than ``K``
+        unflagged samples, 2 skipped for a pivot."""
+        out = D.empty(self.ndet * self.nchunks, torch.uint8)
+        _hip.call("cm2_template_status", self._handle.h, D.ptr(out), D.stream())
+        return D.to_host(out).reshape(self.ndet, self.nchunks)
+
+    def template_tables(self):
+        """The table ``[J, ns]`` as the handle holds it (an HBM tensor): centred per chunk with the constant, the
+        caller's values without."""
+        out = D.empty(self.J * self.ns)
+        if self.J:
+            _hip.call("cm2_template_tables", self._handle.h, D.ptr(out), D.stream())
+        return out.reshape(self.J, self.ns)
 
 
 # ========================================================== CommonModeFilterLO ===

@@ -941,6 +941,79 @@ int cm2_demod_run(cm2_demod *h, const double *d_in, const double *d_cos, const d
 int cm2_demod_pick(const cm2_demod *h, const int32_t *d_pix, const uint8_t *d_class, int drop_from, int32_t *d_out,
                    void *stream);
 
+/* ---- f2i: template filter  (TemplateFilterLO) --------------------------------------------------
+ * Fits and removes time-domain templates given by the caller, per detector and chunk: a stage thermometer, the air
+ * mass 1 / sin(el) (the fitted coefficient of an elevation nod is the relative gain), accelerometer and encoder
+ * channels, a scan-synchronous template sampled in time.  It is f2c with the harmonic table replaced by
+ * d_templates[J][ns], J = ntemplates, shared by all detectors.  No counterpart in the reference: the definition is the
+ * one below.
+ * Layout, flags, chunk edges and units as in f2c.  K = J + 1 with the constant (add_constant = 1), K = J without
+ * (add_constant = 0); 1 <= K <= CM2_TEMPLATE_MAX_K.
+ *     With the constant:    T_0 = 1,  T_j(t) = d_templates[j - 1][t] - mu_{j,c}   (j = 1..J, t in chunk c),
+ *     without it:           T_j(t) = d_templates[j][t]                            (j = 0..J-1), as given.
+ * mu_{j,c} is the mean of template j over the finite values of ALL samples of chunk c.  The flags do not enter: they
+ * differ by detector, the table does not.  Centring does not change out (the constant spans the difference); it is
+ * there for the skip rule: a thermometer reading 0.1 K +- 1e-5 is collinear with the constant to 1e-8 and would fail
+ * the pivot test in every unit.  c_0 is therefore the offset AT THE CHUNK MEAN of the templates, not at template
+ * value 0; the other coefficients are those of the templates as given.
+ * Per unit, V its unflagged samples and m = |V|: G, b, c = G^-1 b and out as in f2c,
+ *     out_t = v_t - T(t)^T c on V,  out_t = 0 on the flagged samples of the unit
+ * (M - M T G^-1 T^T M: symmetric and idempotent).
+ * A unit is SKIPPED -- every sample of it 0 in the output, its K coefficients 0 -- when m < K (mark 1), or when the
+ * Cholesky factorisation meets a pivot that fails !(p_j > CM2_TEMPLATE_TAU G_jj) (mark 2): two templates equal on
+ * the chunk, a template constant on a chunk next to the constant.  A non-finite template value on an unflagged sample
+ * of a unit makes G non-finite, the pivot test fails and the unit is skipped with mark 2: this falls out of the test as
+ * written and takes no extra pass.  A non-finite template value on samples that are flagged for a detector has no
+ * effect on that detector's unit.  A non-finite v_t on an unflagged sample makes its own unit's output non-finite and
+ * no other unit's.
+ *
+ * G depends on the templates and the flags only: it is formed and factorised on the device by cm2_template_create.
+ * The handle holds its own copy of the table, centred (J ns doubles, the only state of that size: the caller's array
+ * may go away), the factors (K (K + 1) / 2 doubles per unit), the marks and the segment sums of one application
+ * (K doubles per segment).
+ *
+ * Order of the sums (no floating-point atomics; the same bits every time), per detector that of f2c: segments of 4096
+ * samples, thread t adds T_j(q) v_q over its unflagged samples q = t, t + 256, ... in ascending order, starting from
+ * 0; the 64 lanes of a wave by x += x[lane + off], off = 32, 16, 8, 4, 2, 1; the four waves as ((w0 + w1) + w2) + w3;
+ * a unit's segments in ascending order, starting from 0.  The Gram sums are formed the same way; m is an integer
+ * count.  mu_{j,c}: thread t of one workgroup adds the finite x_q, q = t, t + 256, ... of the whole chunk in ascending
+ * order, starting from 0; lanes and waves as above; mu = sum / (number of finite values), 0 when there is none;
+ * T = x - mu.  Then the two triangular solves as in f2c and
+ * out_t = v_t - (((c_0 T_0 + c_1 T_1) + c_2 T_2) + ... + c_{K-1} T_{K-1}), where c_0 T_0 is c_0 with the constant.
+ * Every product and sum is rounded on its own.  A workgroup works on one segment of several consecutive detectors
+ * at once, so that a template value is loaded once for all of them (8 K / Dt bytes per detector sample and pass,
+ * Dt = 4 for K <= 2 and 2 above); no sum depends on that grouping.
+ *
+ * cm2_template_create keeps d_pix (it must not change or be freed while the handle lives) and copies d_templates
+ *   (device memory, J ns doubles; may be NULL when J = 0) and h_edges[nchunks + 1].  Allocates and synchronises.
+ * cm2_template_info: h_info[10] = ns, ndet, nchunks, K, add_constant, units fitted, units skipped for m < K, units
+ *   skipped for a pivot, segment size, segments.
+ * cm2_template_apply: d_out = F d_in (nt doubles each).  Three launches, no allocation, no synchronisation.  One handle
+ *   runs one apply or fit at a time.
+ * cm2_template_fit: d_coeff[ndet nchunks K] = the coefficients c of every unit, without the subtract pass.
+ * cm2_template_status: d_status[ndet nchunks] = the mark of every unit, one byte each: CM2_TEMPLATE_FITTED,
+ *   CM2_TEMPLATE_FEW, CM2_TEMPLATE_PIVOT.  A copy on the stream.
+ * cm2_template_tables: copies the handle's table to d_tables[J][ns] (nothing when J = 0).
+ * Refused with CM2_ERR_ARGUMENT, the outputs (and *out) untouched: ntemplates < 0; add_constant other than 0 or 1;
+ * K outside [1, 16]; ns, ndet or nchunks < 1; edges that do not ascend strictly from 0 to ns; NULL pointers; sizes that
+ * overflow the index types (ns >= 2^40, ndet ns > 2^46, 2^31 or more segments or units); d_out or d_coeff sharing
+ * memory with d_in. */
+#define CM2_TEMPLATE_TAU 0.0009765625       /* 2^-10 */
+#define CM2_TEMPLATE_MAX_K 16
+#define CM2_TEMPLATE_FITTED 0
+#define CM2_TEMPLATE_FEW 1
+#define CM2_TEMPLATE_PIVOT 2
+typedef struct cm2_template cm2_template;
+int cm2_template_create(cm2_template **out, int64_t ns, int ndet, int64_t nchunks, const int64_t *h_edges,
+                        int ntemplates, const double *d_templates, int add_constant, const int32_t *d_pix,
+                        void *stream);
+int cm2_template_destroy(cm2_template *h);
+int cm2_template_info(const cm2_template *h, int64_t *h_info);
+int cm2_template_apply(cm2_template *h, const double *d_in, double *d_out, void *stream);
+int cm2_template_fit(cm2_template *h, const double *d_in, double *d_coeff, void *stream);
+int cm2_template_status(const cm2_template *h, uint8_t *d_status, void *stream);
+int cm2_template_tables(const cm2_template *h, double *d_tables, void *stream);
+
 /* ---- f3: solution vector <-> full-sky HEALPix maps -------------------------------
  * cm2_cutsky_to_fullsky: d_full is pol arrays of nfull doubles one after the other
  * ([I | Q | U]); component k of observed pixel i, d_map[pol*i + k], goes to
