@@ -199,6 +199,13 @@ PROTOTYPES = {
     "cm2_template_fit": [_vp, _vp, _vp, _vp],
     "cm2_template_status": [_vp, _vp, _vp],
     "cm2_template_tables": [_vp, _vp, _vp],
+    "cm2_fourier_create": [ctypes.POINTER(_vp), _i64, ctypes.POINTER(_i64), _i64, _dbl, ctypes.POINTER(_dbl), _int, _dbl,
+                           _int, _dbl, _int, ctypes.POINTER(_dbl), _int, ctypes.POINTER(_dbl), _i64, _int, _int, _int,
+                           _int, _i64, _int, _i64, _vp],
+    "cm2_fourier_destroy": [_vp],
+    "cm2_fourier_info": [_vp, ctypes.POINTER(_i64), _vp],
+    "cm2_fourier_apply": [_vp, _vp, _vp, _vp],
+    "cm2_fourier_response": [_vp, _i64, _vp, _vp],
 }
 _RESTYPE = {"cm2_last_error": ctypes.c_char_p, "cm2_reduce_work_doubles": _i64,
             "cm2_gemm_tn_work_doubles": _i64, "cm2_pca_cov_doubles": _i64}
@@ -256,7 +263,7 @@ ERR_OUT_OF_MEMORY = 3          # CM2_ERR_OUT_OF_MEMORY of include/cosmomap2.h
 # build frees what it had made) or overwrite their outputs from their inputs.  NOT in the list: the in-place
 # updates (cm2_axpy, cm2_scal, cm2_Z_axpy, cm2_panel_gemm with accumulate, cm2_pcg_update_*,
 # cm2_flag_samples, cm2_compact_*, cm2_noise_sim_draw with add, cm2_cmode_apply whose output may be its input,
-# cm2_glitch_apply_pix, cm2_jump_correct and cm2_pca_apply whose output may be its input),
+# cm2_glitch_apply_pix, cm2_jump_correct, cm2_pca_apply and cm2_fourier_apply whose output may be its input),
 # which a second run would apply twice, and the drivers with callbacks (cm2_pcg, cm2_pcg_sharded, cm2_arnoldi).
 RESTARTABLE = frozenset([
     "cm2_pointing_create", "cm2_pointing_build_sell", "cm2_pointing_set_weights",
@@ -288,6 +295,7 @@ RESTARTABLE = frozenset([
     "cm2_pca_create", "cm2_pca_cov", "cm2_pca_set_modes", "cm2_pca_fit", "cm2_pca_status",
     "cm2_demod_create", "cm2_demod_destroy", "cm2_demod_info", "cm2_demod_run", "cm2_demod_pick",
     "cm2_template_create", "cm2_template_apply", "cm2_template_fit", "cm2_template_status", "cm2_template_tables",
+    "cm2_fourier_create", "cm2_fourier_response",
 ])
 
 

@@ -31,7 +31,7 @@ torch = D.torch
 __all__ = ["SparseLO", "ToeplitzLO", "BlockLO", "BlockDiagonalLO",
            "BlockDiagonalPreconditionerLO", "InverseLO", "CoarseLO", "DeflationLO",
            "TwoLevelPreconditionerLO", "FilterLO", "GroundFilterLO", "HWPSSFilterLO", "hwpss_plan",
-           "TemplateFilterLO", "CommonModeFilterLO", "cmode_groups", "focalplane_modes", "PCAFilterLO", "pca_select_modes",
+           "TemplateFilterLO", "FourierFilterLO", "CommonModeFilterLO", "cmode_groups", "focalplane_modes", "PCAFilterLO", "pca_select_modes",
            "set_pointing_mode", "lp"]
 
 _I64P = ctypes.POINTER(ctypes.c_int64)
@@ -1387,6 +1387,65 @@ class TemplateFilterLO(_TimeFilter):
         if self.J:
             _hip.call("cm2_template_tables", self._handle.h, D.ptr(out), D.stream())
         return out.reshape(self.J, self.ns)
+
+
+# ============================================================= FourierFilterLO ===
+class FourierFilterLO(_TimeFilter):
+    """
+    The Fourier filter of :class:`cosmomap2_amd.utilities.FourierFilter` as a ``(nt, nt)`` operator (include/cosmomap2.h,
+    f2j): per noise block the transform is multiplied by ``H_b(f)`` -- time-constant deconvolution or convolution,
+    Butterworth low- and high-pass, notches, a tabulated response -- and transformed back.  No counterpart in the
+    reference.
+
+    ``FourierFilterLO(blocksize, fsample, tau=None, mode="deconvolve", lowpass=None, highpass=None, notch=(),
+    response=None, detrend="none", end_mean=32, pad=1024, max_work_bytes=None)``: the arguments of ``FourierFilter``;
+    ``blocksize`` must say the length of the stream (the list of block sizes, or ``nt=`` beside an int).  With
+    ``detrend="none"`` the operator is linear and its transpose is the filter with ``conj(H)``; it is symmetric when
+    ``H`` is real (no time constant and no complex table): ``P.T * F * P`` is then a filter-and-bin normal operator.
+    With ``detrend="ends"`` the trend passes around the filter and the operator has no transpose here: ``rmatvec``
+    raises.  The stage takes no flags (fill the gaps first), so it may stand between a tile-order ``P`` and ``P^T``
+    for any ``P``; it runs in time order there.
+    """
+
+    def __init__(self, blocksize, fsample, tau=None, mode="deconvolve", lowpass=None, highpass=None, notch=(),
+                 response=None, detrend="none", end_mean=32, pad=1024, max_work_bytes=None, nt=None):
+        from ..utilities.fourier_filter import FourierFilter
+        kw = dict(tau=tau, mode=mode, lowpass=lowpass, highpass=highpass, notch=notch, response=response,
+                  detrend=detrend, end_mean=end_mean, pad=pad, max_work_bytes=max_work_bytes)
+        self._filter = FourierFilter(blocksize, fsample, **kw)
+        if nt is None:
+            if np.ndim(blocksize) == 0:
+                raise ValueError("blocksize=%r does not say how long the stream is: give nt" % (blocksize,))
+            nt = sum(self._filter.blocksize)
+        self.n = int(nt)
+        self._filter._sizes(self.n)
+        self.linear = detrend == "none"
+        self._transposed = FourierFilter(blocksize, fsample, conjugate=True, **kw) if self.linear else None
+        super(FourierFilterLO, self).__init__(nargin=self.n, nargout=self.n, matvec=self.mult,
+                                              rmatvec=self.rmult,
+                                              symmetric=self.linear and self._filter.real_response)
+
+    def mult(self, d):
+        return self._filter.apply(self._input_like(d))
+
+    def rmult(self, d):
+        if not self.linear:
+            raise ValueError("FourierFilterLO with detrend='ends' has no transpose: build it with detrend='none'")
+        return self._transposed.apply(self._input_like(d))
+
+    def _input_like(self, d):
+        if _size(d) != self.n:
+            raise lp.ShapeError("time-domain vector has %d entries, expected %d" % (_size(d), self.n))
+        return d
+
+    def response(self, block):
+        return self._filter.response(block, self.n)
+
+    def filter_info(self):
+        return self._filter.info(self.n)
+
+    def _tile_compatible(self, P):
+        return True                 # no flags of its own: nothing to match
 
 
 # ========================================================== CommonModeFilterLO ===

@@ -26,7 +26,7 @@ NO_SPILL = [r"\bk_os_real<", r"\bk_P_tiles", r"\bk_Pt_tiles", r"\bk_Pt_hot", r"\
             r"\bk_Z_axpy_wide", r"\bk_filter_windows", r"\bk_psd_", r"\bk_bands_",
             r"\bk_rng_fill", r"\bk_sim_interior", r"\bk_gap_", r"\bk_offsets_", r"\bk_oprior_",
             r"\bk_gsum_", r"\bk_pexp", r"\bk_hwpss_", r"\bk_cmode_", r"\bk_glitch_",
-            r"\bk_jump_", r"\bk_pca_", r"\bk_demod_", r"\bk_template_"]
+            r"\bk_jump_", r"\bk_pca_", r"\bk_demod_", r"\bk_template_", r"\bk_fourier_"]
 
 # kernels that must not spill SGPRs to VGPR lanes either: the overlap-save instantiations the default dispatch
 # reaches below 4 GB of TOD (at 246-254 of 256 VGPRs a lane register spent on spilled scalars is one too many);

@@ -13,3 +13,4 @@ from .pointing_expand import *                               # noqa: F401,F403
 from .glitches import *                                      # noqa: F401,F403
 from .jumps import *                                         # noqa: F401,F403
 from .demodulate import *                                   # noqa: F401,F403
+from .fourier_filter import *                               # noqa: F401,F403

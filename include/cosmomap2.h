@@ -1014,6 +1014,84 @@ int cm2_template_fit(cm2_template *h, const double *d_in, double *d_coeff, void 
 int cm2_template_status(const cm2_template *h, uint8_t *d_status, void *stream);
 int cm2_template_tables(const cm2_template *h, double *d_tables, void *stream);
 
+/* ---- f2j: Fourier filter per noise block  (FourierFilter, fourier_filter, deconvolve_time_constant,
+ *           FourierFilterLO) --------------------------------------------------------------------------
+ * Multiplies the transform of every noise block by a response H_b(f): the inverse (or, for simulations, the forward)
+ * one-pole response 1 / (1 + 2 pi i f tau_b) of a bolometer, a Butterworth low-pass and high-pass, cos^2 notches and an
+ * arbitrary tabulated response, real or complex.  No counterpart in the reference: the definition is the one below.
+ * The stage takes no flags: gaps are to be filled beforehand (cm2_gaps_fill_linear, GapFiller).
+ * Inputs: d[nt]; noise blocks of sizes[0..nblocks-1] samples adding up to nt (BlockLO's convention), block b the n
+ * samples x_0 .. x_{n-1}; the sample rate fs > 0.  Every operation on doubles named below is rounded once (no fused
+ * multiply-add).
+ *  1. Bad blocks.  A block with any non-finite input sample is bad: every one of its outputs is the quiet NaN
+ *     0x7FF8000000000000, written by the unpack kernel (the transform is not left to decide what such a block
+ *     holds).  cm2_fourier_info counts the bad blocks of the last apply.  No other block is affected.
+ *  2. Trend.  detrend = 0: l = 0.  detrend = 1 (ends): m = min(end_mean, n), 1 <= end_mean <= 1024; a = the mean of
+ *     the first m samples, b = the mean of the last m, each formed by one workgroup: thread t adds the samples t,
+ *     t + 256, ... of the m in ascending order from 0.0, the 64 lanes of a wave by x += x[lane + off], off = 32, 16,
+ *     8, 4, 2, 1, the four waves as ((w0 + w1) + w2) + w3, then one division by m.
+ *     l_i = a + ((b - a) i) / (n - 1);  for n = 1, l_0 = a.
+ *  3. Length.  L = fft_length(n, pad): the smallest even integer >= max(2, n + pad) whose prime factors all lie in
+ *     {2, 3, 5, 7}; 0 <= pad, L <= 2^28.  xt_i = x_i - l_i for i < n and +0.0 for n <= i < L.  (The padding keeps the
+ *     circular convolution from wrapping the end of a block onto its start: a high-pass at f_c wants pad >~ fs / f_c.)
+ *  4. Response at bin k = 0 .. L/2:  f = (k fs) / L  and  H_b(f) = T g R  with
+ *     T: tau_b >= 0 finite, one per block.  tau_b = 0: T = 1.  Otherwise u = ((2 pi) f) tau_b and
+ *        mode 0 (deconvolve): T = 1 + i u;  mode 1 (convolve): T = 1 / (1 + u u) - i u / (1 + u u).
+ *     g = 1, then multiplied in this order by
+ *        G_lp = 1 / sqrt(1 + w), r = (f / f_lp)^2, w = r multiplied p - 1 times by r, 1 <= p <= 16; absent for f_lp = 0;
+ *        G_hp = 0 at k = 0, otherwise the same with r = (f_hp / f)^2 and the order q; absent for f_hp = 0;
+ *        G_notch,j for j = 0 .. J - 1, J <= 16, from (f0_j, w_j > 0): a = |f - f0_j| / w_j; sin^2((pi / 2) a) where
+ *        a < 1 and exactly 1 elsewhere.
+ *     H = (Re T g, Im T g), then times R when a table is given: Rn >= 2 values shared by all blocks (table_per_block
+ *        0, [Rn]) or per block (1, [nblocks][Rn]) on the grid f_r = r (fs / 2) / (Rn - 1), real (table_kind 1) or
+ *        complex (table_kind 2, re and im interleaved), all finite; s = (f / (fs / 2)) (Rn - 1), r = min(floor s,
+ *        Rn - 2), t = s - r, R = R_r + t (R_{r+1} - R_r) in the real and in the imaginary part.  A real R scales both
+ *        parts of H; a complex one multiplies as (re re - im im, re im + im re).
+ *     conjugate = 1 replaces H by its conjugate: the transposed operator (for detrend = 0).
+ *     At k = 0 and k = L/2 the imaginary part of H is set to +0.0.  (The transform of a real stream is real there.
+ *     Convolve followed by deconvolve on an unpadded block is therefore the identity at every bin but the Nyquist
+ *     one, which keeps the factor 1 / (1 + u u).)
+ *  5. Output.  y_i = (1/L) sum_k H_b(f_k) Xt_k e^{2 pi i i k / L}, the real inverse transform of the product (the
+ *     unnormalised inverse divided by L), for i < n, and out_i = y_i + Re H_b(0) l_i (detrend = 0: out_i = y_i).
+ *     The trend goes through the filter as a constant would: the constant tau slope fs that a deconvolved ramp would
+ *     carry is NOT restored.
+ * The transforms are rocFFT's: the result is the definition's to rounding (tests/_fourier_ref.py has the bound), and
+ * has the same bits run to run (no floating-point atomics).
+ *
+ * cm2_fourier_create copies h_sizes, h_tau[nblocks] (NULL: every tau 0), h_notch[J][2] and the table.  It groups the
+ *   blocks by L (at most 8 distinct lengths) and makes one plan per length for a batch of rows, one row = one block:
+ *   L doubles and L/2 + 1 double2.  A batch is at most 2^24 / L rows and at most what max_work_bytes (<= 0: 512 MB)
+ *   holds together with the plan's own work buffer; it is halved until that fits, and a single row that does not fit
+ *   is refused with the bytes it needs.  The rows are shared by all lengths.  Allocates and synchronises.
+ * cm2_fourier_apply: d_out[nt] = F d_in[nt]; d_out may be d_in itself.  No allocation, no synchronisation.  One handle
+ *   runs one apply at a time.
+ * cm2_fourier_response: d_H[L/2 + 1][2] = H_block as the filter kernel evaluates it, L the length of that block.
+ * cm2_fourier_info: h_info[29] = nt, nblocks, number of lengths, bytes of the rows and plans, bad blocks of the last
+ *   apply (reads them back: synchronises the stream), then 8 lengths, their 8 batches and their 8 block counts (0
+ *   beyond the number of lengths).
+ * Refused with CM2_ERR_ARGUMENT, the outputs (and *out) untouched: nt < 1 or nt >= 2^32 - 1; sizes that are not
+ * positive or do not add up to nt; more than 2^18 blocks; fs not finite or <= 0; mode or conjugate other than 0, 1; a
+ * tau that is negative or not finite; a cut-off that is negative or not finite, an order outside [1, 16]; more than 16
+ * notches, an f0 that is not finite, a width that is not finite or <= 0; table_kind outside 0..2, Rn < 2, a table value
+ * that is not finite; detrend other than 0, 1; end_mean outside [1, 1024]; pad < 0 or an L beyond 2^28; more than 8
+ * lengths; a row that does not fit; NULL pointers (h_tau, h_notch with J = 0 and the table with kind 0 may be NULL);
+ * a block outside [0, nblocks); d_out overlapping d_in other than being d_in. */
+#define CM2_FOURIER_DECONVOLVE 0
+#define CM2_FOURIER_CONVOLVE 1
+#define CM2_FOURIER_MAX_ORDER 16
+#define CM2_FOURIER_MAX_NOTCH 16
+#define CM2_FOURIER_MAX_END_MEAN 1024
+#define CM2_FOURIER_MAX_LENGTHS 8
+typedef struct cm2_fourier cm2_fourier;
+int cm2_fourier_create(cm2_fourier **out, int64_t nt, const int64_t *h_sizes, int64_t nblocks, double fs,
+                       const double *h_tau, int mode, double f_lp, int p, double f_hp, int q, const double *h_notch,
+                       int nnotch, const double *h_table, int64_t Rn, int table_kind, int table_per_block, int detrend,
+                       int end_mean, int64_t pad, int conjugate, int64_t max_work_bytes, void *stream);
+int cm2_fourier_destroy(cm2_fourier *h);
+int cm2_fourier_info(const cm2_fourier *h, int64_t *h_info, void *stream);
+int cm2_fourier_apply(cm2_fourier *h, const double *d_in, double *d_out, void *stream);
+int cm2_fourier_response(const cm2_fourier *h, int64_t block, double *d_H, void *stream);
+
 /* ---- f3: solution vector <-> full-sky HEALPix maps -------------------------------
  * cm2_cutsky_to_fullsky: d_full is pol arrays of nfull doubles one after the other
  * ([I | Q | U]); component k of observed pixel i, d_map[pol*i + k], goes to
