@@ -1,7 +1,7 @@
-// cm2_fit.h -- the small least-squares fit of the time-stream filters (cm2_hwpss.hip, and cm2_modefit.h for
-// cm2_cmode.hip and cm2_pca.hip), written once: the Cholesky factor with its pivot rule, the two triangular solves,
-// the packed lower triangle and the rule of an edge list.  Plain C++17 with no HIP include of its own: the kernels
-// inline it, and tests/test_fit_header_cpu.py compiles it with the host compiler and compares it bit for bit with
+// cm2_fit.h -- the small least-squares fit of the time-stream filters (cm2_chunkfit.h for cm2_hwpss.hip and
+// cm2_template.hip, cm2_modefit.h for cm2_cmode.hip and cm2_pca.hip), written once: the Cholesky factor with its
+// pivot rule, the two triangular solves, the packed lower triangle and the rule of an edge list.  Plain C++17 with
+// no HIP include of its own: the kernels inline it, and tests/test_fit_header_cpu.py compiles it with the host compiler and compares it bit for bit with
 // tests/_fit_ref.py.
 //
 // The order of every operation (compile with -ffp-contract=off: every product and every sum is rounded on its own):

@@ -1,7 +1,8 @@
 // cm2_template.hip -- the template filter (TemplateFilterLO), see include/cosmomap2.h (f2i): per (detector, chunk)
 // unit, fit and remove K time-domain templates given by the caller (housekeeping channels, the air mass, a
 // scan-synchronous template sampled in time), shared by all detectors, on the unflagged samples.
-// cm2_template_policy.h has the segment plan and the detector tiles.
+// cm2_chunkfit.h has the order of every sum, the factor, the solve and the rule of a skipped unit (tau =
+// CM2_TEMPLATE_TAU; m is an integer count, k_template_count); cm2_template_policy.h has the detector tiles.
 //
 // Templates of a sample, from the table tab[J][ns] of the handle: with the constant T_0 = 1 and T_j = tab[j - 1]
 // (the caller's template minus its chunk mean, k_template_centre); without it T_j = tab[j], as given.
@@ -12,55 +13,28 @@
 // Dt x K accumulators (32 doubles at most).  The table costs 8 K / Dt bytes per detector sample and pass from L2
 // instead of 8 K.  Workgroups run tiles fastest, so that those in flight together read the same lines of the table.
 //
-// The order of every sum, per detector and independent of the tile (segment sums of T_j v in k_template_sums<K, false>,
-// of T_i T_j in k_template_sums<K, true>):
-//   1. thread t of the segment's workgroup: acc = 0, then acc += T_j(q) v(q) for its unflagged samples
-//      q = t, t + 256, ... in ascending order (kPer = 16 at most);
-//   2. the 64 lanes of a wave: x += shfl_down(x, off) for off = 32, 16, 8, 4, 2, 1; lane 0 holds the wave's sum;
-//   3. the segment's sum is ((w0 + w1) + w2) + w3 of its four waves;
-//   4. a unit's sum is 0 + its segments' sums in ascending segment order (k_template_solve, k_template_factor).
-// There is no floating-point atomic: two applications give the same bits.
+// The sums are formed per detector and do not depend on the tile (segment sums of T_j v in k_template_sums<K, false>,
+// of T_i T_j in k_template_sums<K, true>).
 //
 // Centring (k_template_centre, once, with the constant only): one workgroup per (template, chunk).  Thread t adds the
 // finite values x(q), q = t, t + 256, ... of the whole chunk in ascending order, starting from 0, and counts them;
-// lanes and waves as in 2. and 3.; mu = sum / count (0 when none is finite); tab(q) = x(q) - mu for every q.
-// Factor (k_template_factor, once) and solve (k_template_solve): cm2_fit.h has them and the order of their operations;
-// the unit is skipped when a pivot fails with tau = CM2_TEMPLATE_TAU, or when it has m < K unflagged samples (m is an
-// integer count, k_template_count).
+// lanes and waves as in steps 2 and 3 of the sum order; mu = sum / count (0 when none is finite); tab(q) = x(q) - mu
+// for every q.
 // Subtract (k_template_subtract): p = c_0 T_0, then p += c_j T_j for j = 1..K-1 (c_0 T_0 = c_0 exactly where T_0 = 1);
 // out = v - p on an unflagged sample, 0 on a flagged one and on every sample of a skipped unit.
-#include "cm2_common.h"
+#include "cm2_chunkfit.h"
 #include "cm2_template_policy.h"
-
-#include <vector>
 
 using namespace cm2;
 namespace tp = cm2::tmpl;
+namespace cf = cm2::chunkfit;
 
 namespace {
 
-struct PlanDev {
-    int64_t ns, ndet, nchunks, segs_per_det, ntiles;
+struct PlanDev : cf::GeomDev {
+    int64_t ntiles;
     int cst;                                           // 1 with the constant: T_0 = 1 and row j of the table is T_{j+1}
-    const int64_t *edges, *seg_first;
-    const int32_t *seg_chunk;
 };
-
-struct GroupPos {
-    int64_t t0, t1;      // samples [t0, t1) of the row
-    int64_t r, c;        // row segment, chunk
-};
-
-__device__ __forceinline__ GroupPos group_pos(const PlanDev &p, int64_t w)
-{
-    GroupPos s;
-    s.r = w / p.ntiles;
-    s.c = p.seg_chunk[s.r];
-    s.t0 = p.edges[s.c] + (s.r - p.seg_first[s.c]) * tp::kSeg;
-    const int64_t e = p.edges[s.c + 1];
-    s.t1 = s.t0 + tp::kSeg < e ? s.t0 + tp::kSeg : e;
-    return s;
-}
 
 template <int K>
 __device__ __forceinline__ void load_templates(const PlanDev &p, const double *__restrict__ tab, int64_t t,
@@ -110,13 +84,9 @@ __global__ __launch_bounds__(tp::kThreads) void k_template_count(PlanDev p, cons
 {
     __shared__ int wn[4];
     const int64_t b = blockIdx.x;
-    const int64_t det = b / p.segs_per_det, r = b - det * p.segs_per_det;
-    const int64_t c = p.seg_chunk[r];
-    const int64_t t0 = p.edges[c] + (r - p.seg_first[c]) * tp::kSeg;
-    const int64_t e = p.edges[c + 1];
-    const int64_t t1 = t0 + tp::kSeg < e ? t0 + tp::kSeg : e;
+    const cf::SegPos s = cf::seg_pos(p, b);
     int n = 0;
-    for (int64_t t = t0 + threadIdx.x; t < t1; t += tp::kThreads) n += pix[det * p.ns + t] >= 0 ? 1 : 0;
+    for (int64_t t = s.t0 + threadIdx.x; t < s.t1; t += tp::kThreads) n += pix[s.base + t] >= 0 ? 1 : 0;
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) n += __shfl_down(n, off, 64);
     if ((threadIdx.x & 63) == 0) wn[threadIdx.x >> 6] = n;
@@ -137,7 +107,7 @@ __global__ __launch_bounds__(tp::kThreads, 2) void k_template_sums(PlanDev p, co
     constexpr int Dt = tp::det_tile(K);
     __shared__ double wsum[Dt][4][K];
     const int64_t w = blockIdx.x;
-    const GroupPos s = group_pos(p, w);
+    const cf::RowSeg s = cf::row_segment(p, w / p.ntiles);
     const int64_t k0 = (w - s.r * p.ntiles) * Dt;
     const int row = GRAM ? (int)blockIdx.y : 0;
     bool live[Dt];
@@ -176,23 +146,15 @@ __global__ __launch_bounds__(tp::kThreads, 2) void k_template_sums(PlanDev p, co
         }
     }
     // steps 2 and 3 of the sum order, detector by detector
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 #pragma unroll
-    for (int d = 0; d < Dt; ++d) {
-        if (live[d]) {
-#pragma unroll
-            for (int j = 0; j < K; ++j) {
-                const double x = wave_sum(acc[d][j]);
-                if (lane == 0) wsum[d][wv][j] = x;
-            }
-        }
-    }
+    for (int d = 0; d < Dt; ++d)
+        if (live[d]) cf::wave_sums<K>(acc[d], wsum[d]);
     __syncthreads();
     for (int e = threadIdx.x; e < Dt * K; e += tp::kThreads) {
         const int d = e / K, j = e - d * K;
         if (k0 + d < p.ndet && (GRAM || !skip[(k0 + d) * p.nchunks + s.c])) {
             const int64_t seg = (k0 + d) * p.segs_per_det + s.r;
-            const double x = ((wsum[d][0][j] + wsum[d][1][j]) + wsum[d][2][j]) + wsum[d][3][j];
+            const double x = cf::waves_sum<K>(wsum[d], j);
             if (GRAM) dst[(seg * K + row) * K + j] = x;
             else dst[seg * K + j] = x;
         }
@@ -200,62 +162,22 @@ __global__ __launch_bounds__(tp::kThreads, 2) void k_template_sums(PlanDev p, co
 }
 
 // one workgroup of 64 threads per unit: adds the counts and the Gram sums of its segments, factorises, marks
-// skip = 0 fitted, 1 fewer than K unflagged samples, 2 a pivot that fails !(p > tau G_jj)
 __global__ __launch_bounds__(64) void k_template_factor(PlanDev p, int K, double tau, const int32_t *__restrict__ cnt,
                                                          const double *__restrict__ gp, double *__restrict__ factor,
                                                          uint8_t *__restrict__ skip)
 {
-    __shared__ double G[tp::kMaxK * tp::kMaxK];
-    const int64_t unit = blockIdx.x;
-    const int64_t det = unit / p.nchunks, c = unit - det * p.nchunks;
-    const int64_t first = det * p.segs_per_det + p.seg_first[c];
-    const int64_t nseg = p.seg_first[c + 1] - p.seg_first[c];
-    const int KK = K * K;
-    for (int e = threadIdx.x; e < KK; e += 64) {
-        double sum = 0.0;
-        for (int64_t g = 0; g < nseg; ++g) sum += gp[(first + g) * KK + e];
-        G[e] = sum;
-    }
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    int64_t m = 0;
-    for (int64_t g = 0; g < nseg; ++g) m += cnt[first + g];
-    double *L = factor + unit * tp::packed(K);
-    int mark = m < K ? tp::kFew : tp::kFitted;
-    const fit::RowMajor rows{G, K};
-    if (mark == tp::kFitted && fit::factor(K, rows, tau)) mark = tp::kPivot;
-    for (int i = 0; i < K; ++i)
-        for (int j = 0; j <= i; ++j) L[tp::packed_at(i, j)] = mark ? 0.0 : G[i * K + j];
-    skip[unit] = (uint8_t)mark;
+    cf::factor_unit<tp::kMaxK>(p, K, tau, gp, factor, skip, [&](const double *, const cf::UnitSegs &u) {
+        int64_t m = 0;
+        for (int64_t g = 0; g < u.n; ++g) m += cnt[u.first + g];
+        return m;
+    });
 }
 
-// one workgroup of 64 threads per unit: lane j adds the segments' sums of template j, thread 0 solves
 __global__ __launch_bounds__(64) void k_template_solve(PlanDev p, int K, const uint8_t *__restrict__ skip,
                                                         const double *__restrict__ factor,
                                                         const double *__restrict__ partial, double *__restrict__ coeff)
 {
-    __shared__ double y[tp::kMaxK];
-    __shared__ double L[tp::kMaxK * (tp::kMaxK + 1) / 2];
-    const int64_t unit = blockIdx.x;
-    const int j = threadIdx.x;
-    if (skip[unit]) {
-        if (j < K) coeff[unit * K + j] = 0.0;
-        return;
-    }
-    const int64_t det = unit / p.nchunks, c = unit - det * p.nchunks;
-    const int64_t first = det * p.segs_per_det + p.seg_first[c];
-    const int64_t nseg = p.seg_first[c + 1] - p.seg_first[c];
-    for (int e = j; e < tp::packed(K); e += 64) L[e] = factor[unit * tp::packed(K) + e];
-    if (j < K) {
-        double sum = 0.0;
-#pragma unroll 8
-        for (int64_t g = 0; g < nseg; ++g) sum += partial[(first + g) * K + j];
-        y[j] = sum;
-    }
-    __syncthreads();
-    if (j != 0) return;
-    fit::solve(K, L, y);
-    for (int i = 0; i < K; ++i) coeff[unit * K + i] = y[i];
+    cf::solve_unit<tp::kMaxK>(p, K, skip, factor, partial, coeff);
 }
 
 // the coefficients of the tile's units go through LDS once per workgroup, the templates are loaded once per sample
@@ -271,7 +193,7 @@ __global__ __launch_bounds__(tp::kThreads, 2) void k_template_subtract(PlanDev p
     __shared__ double cs[Dt][K];
     __shared__ int gone[Dt];                           // 0 fit, 1 skipped unit (zeros), 2 no such detector
     const int64_t w = blockIdx.x;
-    const GroupPos s = group_pos(p, w);
+    const cf::RowSeg s = cf::row_segment(p, w / p.ntiles);
     const int64_t k0 = (w - s.r * p.ntiles) * Dt;
     for (int e = threadIdx.x; e < Dt * K; e += tp::kThreads) {
         const int d = e / K, j = e - d * K;
@@ -316,23 +238,16 @@ __global__ __launch_bounds__(tp::kThreads, 2) void k_template_subtract(PlanDev p
 struct cm2_template {
     tp::Plan plan;
     const int32_t *d_pix = nullptr;       // borrowed
-    int64_t *d_edges = nullptr, *d_seg_first = nullptr;
-    int32_t *d_seg_chunk = nullptr;
-    double *d_tab = nullptr, *d_factor = nullptr, *d_partial = nullptr, *d_coeff = nullptr;
-    uint8_t *d_skip = nullptr;
-    int64_t nmark[3] = {0, 0, 0};
-    PlanDev dev() const
-    {
-        return PlanDev{plan.ns, plan.ndet, plan.nchunks, plan.segs_per_det, plan.ntiles, plan.add_constant,
-                       d_edges, d_seg_first, d_seg_chunk};
-    }
+    cf::State state;
+    double *d_tab = nullptr;
+    PlanDev dev() const { return PlanDev{state.dev(plan), plan.ntiles, plan.add_constant}; }
 };
 
 extern "C" int cm2_template_destroy(cm2_template *h)
 {
     if (!h) return 0;
-    dev_release(h->d_edges, h->d_seg_first, h->d_seg_chunk, h->d_tab, h->d_factor, h->d_partial, h->d_coeff,
-                h->d_skip);
+    h->state.release();
+    dev_release(h->d_tab);
     delete h;
     return 0;
 }
@@ -344,14 +259,8 @@ int template_fill(cm2_template *h, const double *d_templates, hipStream_t st)
     const tp::Plan &p = h->plan;
     const int K = p.K;
     const size_t ntab = (size_t)p.J * (size_t)p.ns;
-    if (int rc = dev_put(&h->d_edges, p.edges.data(), p.edges.size(), st)) return rc;
-    if (int rc = dev_put(&h->d_seg_first, p.seg_first.data(), p.seg_first.size(), st)) return rc;
-    if (int rc = dev_put(&h->d_seg_chunk, p.seg_chunk.data(), p.seg_chunk.size(), st)) return rc;
+    if (int rc = h->state.fill(p, K, st)) return rc;
     CM2_HIP(cm2::dev_malloc(&h->d_tab, sizeof(double) * (ntab ? ntab : 1)));
-    CM2_HIP(cm2::dev_malloc(&h->d_factor, sizeof(double) * (size_t)(p.nunits * tp::packed(K))));
-    CM2_HIP(cm2::dev_malloc(&h->d_partial, sizeof(double) * (size_t)(p.nsegs * K)));
-    CM2_HIP(cm2::dev_malloc(&h->d_coeff, sizeof(double) * (size_t)(p.nunits * K)));
-    CM2_HIP(cm2::dev_malloc(&h->d_skip, (size_t)p.nunits));
     if (ntab) CM2_HIP(hipMemcpyAsync(h->d_tab, d_templates, sizeof(double) * ntab, hipMemcpyDeviceToDevice, st));
     if (p.add_constant && p.J > 0) {
         k_template_centre<<<dim3((unsigned)p.nchunks, (unsigned)p.J), tp::kThreads, 0, st>>>(h->dev(), h->d_tab);
@@ -368,14 +277,10 @@ int template_fill(cm2_template *h, const double *d_templates, hipStream_t st)
         k_template_sums<KC, true><<<grid, tp::kThreads, 0, st>>>(h->dev(), nullptr, h->d_pix, nullptr, h->d_tab, gp.p);
     });
     CM2_LAUNCH_OK();
-    k_template_factor<<<dim3((unsigned)p.nunits), 64, 0, st>>>(h->dev(), K, CM2_TEMPLATE_TAU, cnt, gp, h->d_factor,
-                                                                h->d_skip);
+    k_template_factor<<<dim3((unsigned)p.nunits), 64, 0, st>>>(h->dev(), K, CM2_TEMPLATE_TAU, cnt, gp,
+                                                                h->state.d_factor, h->state.d_skip);
     CM2_LAUNCH_OK();
-    std::vector<uint8_t> marks((size_t)p.nunits);
-    CM2_HIP(cm2::download(marks.data(), h->d_skip, marks.size(), st));
-    CM2_HIP(hipStreamSynchronize(st));
-    for (uint8_t m : marks) h->nmark[m < 3 ? m : 0]++;
-    return 0;
+    return h->state.tally(p, st);
 }
 
 }  // namespace
@@ -395,12 +300,7 @@ extern "C" int cm2_template_create(cm2_template **out, int64_t ns, int ndet, int
         CM2_CHECK(ps != tp::kBadConstant, "%s: add_constant=%d must be 0 or 1", who, add_constant);
         CM2_CHECK(ps != tp::kBadK, "%s: K = ntemplates + add_constant = %d + %d outside [1, %d]", who, ntemplates,
                   add_constant, tp::kMaxK);
-        CM2_CHECK(ps != tp::kBadSize, "%s: ns=%lld, ndet=%d, nchunks=%lld must all be >= 1", who, (long long)ns, ndet,
-                  (long long)nchunks);
-        CM2_CHECK(ps != tp::kBadEdges, "%s: the %lld chunk edges must ascend strictly from 0 to ns=%lld", who,
-                  (long long)nchunks + 1, (long long)ns);
-        CM2_CHECK(false, "%s: ns=%lld x ndet=%d with %lld chunks overflows the index types", who, (long long)ns, ndet,
-                  (long long)nchunks);
+        return cf::check_create_status(who, ps, tp::kBadSize, ns, ndet, nchunks);
     }
     h->d_pix = d_pix;
     const int rc = template_fill(h, d_templates, as_stream(stream));
@@ -420,9 +320,9 @@ extern "C" int cm2_template_info(const cm2_template *h, int64_t *h_info)
     h_info[2] = h->plan.nchunks;
     h_info[3] = h->plan.K;
     h_info[4] = h->plan.add_constant;
-    h_info[5] = h->nmark[0];
-    h_info[6] = h->nmark[1];
-    h_info[7] = h->nmark[2];
+    h_info[5] = h->state.nmark[0];
+    h_info[6] = h->state.nmark[1];
+    h_info[7] = h->state.nmark[2];
     h_info[8] = tp::kSeg;
     h_info[9] = h->plan.nsegs;
     return 0;
@@ -434,11 +334,11 @@ int template_fit_into(cm2_template *h, const double *d_in, double *d_coeff, hipS
 {
     dispatch_int<1, tp::kMaxK>(h->plan.K, [&](auto KC) {
         k_template_sums<KC, false><<<dim3((unsigned)h->plan.ngroups), tp::kThreads, 0, st>>>(
-            h->dev(), h->d_skip, h->d_pix, d_in, h->d_tab, h->d_partial);
+            h->dev(), h->state.d_skip, h->d_pix, d_in, h->d_tab, h->state.d_partial);
     });
     CM2_LAUNCH_OK();
-    k_template_solve<<<dim3((unsigned)h->plan.nunits), 64, 0, st>>>(h->dev(), h->plan.K, h->d_skip, h->d_factor,
-                                                                     h->d_partial, d_coeff);
+    k_template_solve<<<dim3((unsigned)h->plan.nunits), 64, 0, st>>>(h->dev(), h->plan.K, h->state.d_skip,
+                                                                     h->state.d_factor, h->state.d_partial, d_coeff);
     CM2_LAUNCH_OK();
     return 0;
 }
@@ -461,10 +361,10 @@ extern "C" int cm2_template_apply(cm2_template *h, const double *d_in, double *d
     CM2_CHECK(!ranges_overlap(d_in, h->plan.nt, d_out, h->plan.nt),
               "cm2_template_apply: output must not alias the input");
     hipStream_t st = as_stream(stream);
-    if (int rc = template_fit_into(h, d_in, h->d_coeff, st)) return rc;
+    if (int rc = template_fit_into(h, d_in, h->state.d_coeff, st)) return rc;
     dispatch_int<1, tp::kMaxK>(h->plan.K, [&](auto KC) {
         k_template_subtract<KC><<<dim3((unsigned)h->plan.ngroups), tp::kThreads, 0, st>>>(
-            h->dev(), h->d_skip, h->d_coeff, h->d_pix, d_in, h->d_tab, d_out);
+            h->dev(), h->state.d_skip, h->state.d_coeff, h->d_pix, d_in, h->d_tab, d_out);
     });
     CM2_LAUNCH_OK();
     return 0;
@@ -474,7 +374,8 @@ extern "C" int cm2_template_status(const cm2_template *h, uint8_t *d_status, voi
 {
     CM2_CHECK(h, "cm2_template_status: null handle");
     CM2_CHECK(d_status, "cm2_template_status: null array");
-    CM2_HIP(hipMemcpyAsync(d_status, h->d_skip, (size_t)h->plan.nunits, hipMemcpyDeviceToDevice, as_stream(stream)));
+    CM2_HIP(hipMemcpyAsync(d_status, h->state.d_skip, (size_t)h->plan.nunits, hipMemcpyDeviceToDevice,
+                           as_stream(stream)));
     return 0;
 }
 

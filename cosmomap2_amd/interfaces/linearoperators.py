@@ -1236,7 +1236,40 @@ def hwpss_plan(ns, chunks=None):
     return _edges(ns, chunks, "chunk", "chunk length", "ns")
 
 
-class HWPSSFilterLO(_TimeFilter):
+class _ChunkFitFilter(_TimeFilter):
+    """Base of the filters that fit ``K`` templates per (detector, chunk) unit through one library family
+    ``cm2_<_PREFIX>_*``: the detector count, the stream's size, the chunks, the coefficients and the info record,
+    whose entries ``_INFO`` names."""
+    _PREFIX = _INFO = None
+
+    def _set_ndet(self, ndet):
+        if int(ndet) != ndet or int(ndet) < 1:
+            raise ValueError("ndet must be a positive integer, got %r" % (ndet,))
+        self.ndet = int(ndet)
+
+    def _set_stream(self, pix_samples, chunks, ns_name):
+        """``self.ndet`` and ``self.ns`` are set; ``ns_name``: what the message calls the samples of a detector."""
+        self.n = self.ndet * self.ns
+        if _size(pix_samples) != self.n:
+            raise lp.ShapeError("pix_samples has %d entries, expected ndet * %s = %d"
+                                % (_size(pix_samples), ns_name, self.n))
+        self.edges = hwpss_plan(self.ns, chunks)
+        self.nchunks = int(self.edges.size) - 1
+
+    def filter_info(self):
+        info = (ctypes.c_int64 * len(self._INFO))()
+        _hip.call("cm2_%s_info" % self._PREFIX, self._handle.h, info)
+        return dict(zip(self._INFO, [int(v) for v in info]))
+
+    def coefficients(self, d):
+        """The fitted coefficients ``[ndet, nchunks, K]`` of ``d`` (zeros for a skipped unit); nothing is subtracted."""
+        x = self._input(d)
+        out = D.empty(self.ndet * self.nchunks * self.K)
+        _hip.call("cm2_%s_fit" % self._PREFIX, self._handle.h, D.ptr(x), D.ptr(out), D.stream())
+        return D.like_input(out, d).reshape(self.ndet, self.nchunks, self.K)
+
+
+class HWPSSFilterLO(_ChunkFitFilter):
     """
     HWP-synchronous signal filter: per detector and chunk, fit the harmonics ``1, cos(n chi), sin(n chi)``,
     ``n = 1..nharm``, of the half-wave plate angle to the unflagged samples and subtract them
@@ -1249,24 +1282,19 @@ class HWPSSFilterLO(_TimeFilter):
     samples, or whose harmonics are collinear on them (Cholesky pivot <= 2^-10 of its diagonal entry), is skipped:
     its output and its coefficients are 0; ``filter_info()`` counts them.  Flagged samples are 0 in the output.
     """
-    _ENTRY = "cm2_hwpss_apply"
+    _ENTRY, _PREFIX = "cm2_hwpss_apply", "hwpss"
+    _INFO = ("ns", "ndet", "nchunks", "nharm", "fitted", "skipped_few", "skipped_pivot", "segment", "segments")
 
     def __init__(self, chi, pix_samples, ndet=1, nharm=4, chunks=None):
         if int(nharm) != nharm or not 1 <= int(nharm) <= HWPSS_MAX_HARM:
             raise ValueError("nharm must be an integer in [1, %d], got %r" % (HWPSS_MAX_HARM, nharm))
-        if int(ndet) != ndet or int(ndet) < 1:
-            raise ValueError("ndet must be a positive integer, got %r" % (ndet,))
-        self.nharm, self.ndet = int(nharm), int(ndet)
+        self._set_ndet(ndet)
+        self.nharm = int(nharm)
         self.K = 2 * self.nharm + 1
         if _dims(chi) != 1 or _size(chi) < 1:
             raise lp.ShapeError("chi must be a 1-D array of at least one plate angle")
         self.ns = _size(chi)
-        self.n = self.ndet * self.ns
-        if _size(pix_samples) != self.n:
-            raise lp.ShapeError("pix_samples has %d entries, expected ndet * len(chi) = %d"
-                                % (_size(pix_samples), self.n))
-        self.edges = hwpss_plan(self.ns, chunks)
-        self.nchunks = int(self.edges.size) - 1
+        self._set_stream(pix_samples, chunks, "len(chi)")
         D.require_gpu()
         self._d_pix = D.i32(pix_samples).reshape(-1)
         d_chi = D.f64(chi)
@@ -1276,19 +1304,10 @@ class HWPSSFilterLO(_TimeFilter):
         self._handle = _hip.Handle("cm2_hwpss_destroy", handle, keep=self._d_pix)
         super(HWPSSFilterLO, self).__init__(nargin=self.n, nargout=self.n, matvec=self.mult, symmetric=True)
 
-    def filter_info(self):
-        info = (ctypes.c_int64 * 9)()
-        _hip.call("cm2_hwpss_info", self._handle.h, info)
-        return dict(zip(("ns", "ndet", "nchunks", "nharm", "fitted", "skipped_few", "skipped_pivot",
-                         "segment", "segments"), [int(v) for v in info]))
-
     def coefficients(self, d):
         """The fitted coefficients ``[ndet, nchunks, 2 nharm + 1]`` of ``d`` (zeros for a skipped unit), in the
         order 1, cos chi, sin chi, cos 2 chi, ...; nothing is subtracted."""
-        x = self._input(d)
-        out = D.empty(self.ndet * self.nchunks * self.K)
-        _hip.call("cm2_hwpss_fit", self._handle.h, D.ptr(x), D.ptr(out), D.stream())
-        return D.like_input(out, d).reshape(self.ndet, self.nchunks, self.K)
+        return super(HWPSSFilterLO, self).coefficients(d)
 
     def harmonic_tables(self):
         """``(cos chi, sin chi)`` as the handle holds them (HBM tensors of ``ns`` doubles)."""
@@ -1302,7 +1321,7 @@ TEMPLATE_MAX_K = 16          # CM2_TEMPLATE_MAX_K of include/cosmomap2.h
 TEMPLATE_FITTED, TEMPLATE_FEW, TEMPLATE_PIVOT = 0, 1, 2      # CM2_TEMPLATE_FITTED, _FEW, _PIVOT
 
 
-class TemplateFilterLO(_TimeFilter):
+class TemplateFilterLO(_ChunkFitFilter):
     """
     Template filter: per detector and chunk, fit the caller's time-domain templates (a stage thermometer, the air
     mass ``1 / sin(el)``, accelerometer or encoder channels, a scan-synchronous template sampled in time) to the
@@ -1324,14 +1343,15 @@ class TemplateFilterLO(_TimeFilter):
     beside the constant) or not finite on one of them, is skipped: its output and its coefficients are 0;
     ``filter_info()`` counts them and ``status()`` names them.  Flagged samples are 0 in the output.
     """
-    _ENTRY = "cm2_template_apply"
+    _ENTRY, _PREFIX = "cm2_template_apply", "template"
+    _INFO = ("ns", "ndet", "nchunks", "K", "add_constant", "fitted", "skipped_few", "skipped_pivot", "segment",
+             "segments")
 
     def __init__(self, templates, pix_samples, ndet=1, chunks=None, add_constant=True):
         if not isinstance(add_constant, (bool, np.bool_)):
             raise ValueError("add_constant must be True or False, not %r" % (add_constant,))
-        if int(ndet) != ndet or int(ndet) < 1:
-            raise ValueError("ndet must be a positive integer, got %r" % (ndet,))
-        self.add_constant, self.ndet = bool(add_constant), int(ndet)
+        self._set_ndet(ndet)
+        self.add_constant = bool(add_constant)
         if _dims(templates) not in (1, 2):
             raise lp.ShapeError("templates must be a [J, ns] array (or one template of ns samples)")
         shape = tuple(templates.shape) if hasattr(templates, "shape") else np.shape(templates)
@@ -1342,11 +1362,7 @@ class TemplateFilterLO(_TimeFilter):
         if not 1 <= self.K <= TEMPLATE_MAX_K:
             raise ValueError("%d templates%s make K = %d, outside [1, %d]"
                              % (self.J, " and the constant" if self.add_constant else "", self.K, TEMPLATE_MAX_K))
-        self.n = self.ndet * self.ns
-        if _size(pix_samples) != self.n:
-            raise lp.ShapeError("pix_samples has %d entries, expected ndet * ns = %d" % (_size(pix_samples), self.n))
-        self.edges = hwpss_plan(self.ns, chunks)
-        self.nchunks = int(self.edges.size) - 1
+        self._set_stream(pix_samples, chunks, "ns")
         D.require_gpu()
         self._d_pix = D.i32(pix_samples).reshape(-1)
         d_tab = D.f64(templates).reshape(-1) if self.J else None
@@ -1357,21 +1373,12 @@ class TemplateFilterLO(_TimeFilter):
         self._handle = _hip.Handle("cm2_template_destroy", handle, keep=self._d_pix)
         super(TemplateFilterLO, self).__init__(nargin=self.n, nargout=self.n, matvec=self.mult, symmetric=True)
 
-    def filter_info(self):
-        info = (ctypes.c_int64 * 10)()
-        _hip.call("cm2_template_info", self._handle.h, info)
-        return dict(zip(("ns", "ndet", "nchunks", "K", "add_constant", "fitted", "skipped_few", "skipped_pivot",
-                         "segment", "segments"), [int(v) for v in info]))
-
     def coefficients(self, d):
         """The fitted coefficients ``[ndet, nchunks, K]`` of ``d`` (zeros for a skipped unit); nothing is subtracted.
         With the constant, ``[:, :, 0]`` is the offset at the chunk mean of the templates and ``[:, :, j]`` the
         coefficient of ``templates[j - 1]``: ``coefficients(d)[:, :, 1]`` of an elevation nod fitted with the air
         mass is the relative gain of every detector."""
-        x = self._input(d)
-        out = D.empty(self.ndet * self.nchunks * self.K)
-        _hip.call("cm2_template_fit", self._handle.h, D.ptr(x), D.ptr(out), D.stream())
-        return D.like_input(out, d).reshape(self.ndet, self.nchunks, self.K)
+        return super(TemplateFilterLO, self).coefficients(d)
 
     def status(self):
         """The class of every unit, ``[ndet, nchunks]`` uint8 on the host: 0 fitted, 1 skipped for fewer than ``K``

@@ -440,3 +440,55 @@ def test_a_drift_does_not_reach_the_map(cm):
           "|m0| = %.3g" % (off, bound, res, left, rho, off_raw, float(np.linalg.norm(m0))))
     assert off <= bound
     assert off_raw >= 100.0 * bound                                      # orders of magnitude without the filter
+
+
+# ---------------------------------------------- the template filter is the HWPSS filter ----
+def hwpss_as_templates(cm, H, seed=11):
+    """HWPSSFilterLO of nharm = H on a small stream, and what TemplateFilterLO needs to be the same filter: the rows
+    [ones, T_1, ..., T_2H] formed on the host from the handle's own (cos chi, sin chi), every product rounded on its
+    own as on the device.  Three detectors (one ragged tile), chunks of K - 1 (too few samples), 300 and kSeg + 1
+    (two segments) samples, a tenth of the samples flagged."""
+    import _hwpss_ref as RH
+    K = 2 * H + 1
+    edges = np.cumsum([0, K - 1, 300, R.SEG + 1]).astype(np.int64)
+    ns, ndet = int(edges[-1]), 3
+    rng = np.random.default_rng(seed + H)
+    chi = 0.37 * np.arange(ns) + 0.01 * rng.standard_normal(ns)
+    pix = np.where(rng.random(ndet * ns) < 0.1, -1, 5).astype(np.int32)
+    v = rng.standard_normal(ndet * ns) + np.tile(3.0 * np.cos(2 * chi + 0.3), ndet)
+    Fh = cm.I.HWPSSFilterLO(chi, pix, ndet=ndet, nharm=H, chunks=edges)
+    c1, s1 = (cm.D.to_host(t) for t in Fh.harmonic_tables())
+    rows = np.ascontiguousarray(RH.templates_f64(c1, s1, H).T)           # [K, ns], row 0 = ones
+    assert np.all(rows[0] == 1.0)
+    return SimpleNamespace(Fh=Fh, rows=rows, pix=pix, v=v, ndet=ndet, edges=edges, K=K)
+
+
+def compare_with_hwpss(cm, H):
+    s = hwpss_as_templates(cm, H)
+    Ft = cm.I.TemplateFilterLO(s.rows, s.pix, ndet=s.ndet, chunks=s.edges, add_constant=False)
+    out_h, out_t = np.asarray(s.Fh * s.v), np.asarray(Ft * s.v)
+    cf_h, cf_t = np.asarray(s.Fh.coefficients(s.v)), np.asarray(Ft.coefficients(s.v))
+    ih, it = s.Fh.filter_info(), Ft.filter_info()
+    marks = Ft.status()
+    assert same_bits(out_h, out_t) and same_bits(cf_h, cf_t)
+    for key in ("fitted", "skipped_few", "skipped_pivot", "segment", "segments"):
+        assert ih[key] == it[key], key
+    # HWPSS has no status call: its marks show in the tally and in which units have coefficients
+    assert (marks[:, 0] == R.FEW).all() and ih["skipped_few"] == s.ndet and ih["fitted"] == 2 * s.ndet
+    assert np.array_equal(marks == R.FITTED, cf_h.any(axis=2)) and np.array_equal(marks == R.FITTED, cf_t.any(axis=2))
+    assert out_h.any() and np.isfinite(out_h).all()
+    return out_h, cf_h, marks
+
+
+@pytest.mark.parametrize("H", (1, 4, 8))
+def test_given_the_harmonic_tables_it_is_the_hwpss_filter(cm, H):
+    """Both filters sum in the order cm2_chunkfit.h states and c_0 * 1.0 is exact: the outputs, the coefficients and
+    the marks are the same bits.  K = 17 of H = 8 is more than the template filter takes: that is refused, and
+    H = 7 (K = 15) is compared instead."""
+    if 2 * H + 1 > cm.L.TEMPLATE_MAX_K:
+        s = hwpss_as_templates(cm, H)
+        with pytest.raises(ValueError) as e:
+            cm.I.TemplateFilterLO(s.rows, s.pix, ndet=s.ndet, chunks=s.edges, add_constant=False)
+        assert "K = 17" in str(e.value)
+        H = 7
+    compare_with_hwpss(cm, H)
